@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - PM grid-points/sec of the HIP pattern-matching path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode grid|stream]
+    python bench.py --gpus N --steps K --warmup W [--mode grid|stream|ftpm] [--full] [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1 works both ways: launched by ``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`` (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or plainly
@@ -35,9 +35,21 @@ touches torch or the GPU (a process that has initialised the GPU is never replac
     stream while the kernels of the previous pair run) and fetches each result block.  A step = the whole
     batch; value = points of all pairs / time, uploads included.  No collective on the data path.
 
-Prints ONE JSON line on rank 0 with a "roofline" object measured live from HIP events around the kernel
-launches and a "cpu_baseline" object (B2 = the C oracle with OpenMP over points, plus B1 = the
-reference-shaped Python/Pool loop under "b1") timed on bounded samples of the same workload.
+A plain run (no --full) sets up, warms up, times the --steps steps and prints ONE JSON line on rank 0: metric, value,
+unit, higher_is_better, dtype, ms_per_step (wall time of one timed step), the workload and a "roofline" object computed
+from the HIP events recorded around the kernel launches of the timed steps.
+
+--full adds everything that is not the headline: in grid mode the weak-scaling figure (N > 1), the reference's default
+configuration ("reference_defaults"), the seam-inclusive timings ("seam_inclusive"), the CPU baselines ("cpu_baseline":
+B2 = the C oracle with OpenMP over points, B1 = the reference-shaped Python/Pool loop under "b1", timed on bounded samples
+of the same workload) and the parity check of the timed output against the C oracle; in stream mode the steady-state
+kernel time of one pair and the parity check; in ftpm mode the parity check.
+
+--dump-outputs DIR writes, after the timed steps, the arrays the timed path returned in its last step as DIR/<name>.npy
+(float64; a fixed, seeded sample of the rows when they exceed 64 MB in all): grid mode results.npy ([N,5]: c2, r2, a, r, h)
+and peak_index.npy ([N,3]: peak row, column and angle index); stream mode the same two per checked pair
+(pair<p>_results.npy, pair<p>_peak_index.npy); ftpm mode the grids u, v, a, r, h, lon2, lat2 and the feature-tracking
+vectors ft_u, ft_v, ft_lon1, ft_lat1, ft_lon2, ft_lat2.  The inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import hashlib
@@ -73,22 +85,27 @@ def parse_args(argv=None):
     ap.add_argument('--img-size', type=int, default=34)
     ap.add_argument('--scaling', choices=('weak', 'strong'), default=None,
                     help='N > 1, grid mode: strong (default) = the same grid sharded; weak = grid rows x N')
-    ap.add_argument('--no-weak', action='store_true', help='skip the secondary weak-scaling measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: weak scaling, the reference defaults, the seam-inclusive '
+                         'timings, the CPU baselines and the parity checks against the C oracle (see the docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument('--no-weak', action='store_true', help='--full: skip the secondary weak-scaling measurement')
     ap.add_argument('--rebalance', type=int, default=3,
                     help='N > 1, strong scaling: rounds of measured feedback on the shard cuts BEFORE the warm-up (every rank times '
                          'its kernels over 3 steps, one all_gather, dist.rebalance_cuts; the cuts with the smallest slowest rank are kept); 0 = the estimated cuts')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-seam', action='store_true', help="skip the seam-inclusive timings (sid_pm_batch host-in / host-out, set_points) reported under 'seam_inclusive'")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
+    ap.add_argument('--no-seam', action='store_true', help="--full: skip the seam-inclusive timings (sid_pm_batch host-in / host-out, set_points) reported under 'seam_inclusive'")
     ap.add_argument('--no-also-defaults', action='store_true',
-                    help="N = 1, grid mode: skip the second measurement on the reference's DEFAULT configuration (img_size 35, "
+                    help="--full, N = 1, grid mode: skip the second measurement on the reference's DEFAULT configuration (img_size 35, "
                          "angles [-3, 0, 3]; pmlib.py:118,329) that is reported under 'reference_defaults'")
     ap.add_argument('--force-collective', action='store_true',
                     help='N = 1: initialise a one-rank nccl (RCCL) group and run the broadcast, the all_reduce and the gathers '
                          'of the N-GPU path on it (exercises the RCCL code path on a one-GPU box)')
     ap.add_argument('--cpu-sample', type=int, default=0,
-                    help='points in the B2 CPU sample (0 = auto: the whole grid when that takes <= ~30 s, else ~12 s worth)')
+                    help='--full: points in the B2 CPU sample (0 = auto: the whole grid when that takes <= ~30 s, else ~12 s worth)')
     ap.add_argument('--check', type=int, default=64,
-                    help='points verified against the oracle after timing when the CPU baseline (which checks the whole grid) is off')
+                    help='--full: points verified against the oracle after timing when the CPU baseline (which checks the whole grid) is off')
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = {'stream': 3, 'ftpm': 5}.get(args.mode, 20)
@@ -134,6 +151,23 @@ def lib_md5():
     from sea_ice_drift_amd import _capi
     with open(_capi.LIB_PATH, 'rb') as fh:
         return hashlib.md5(fh.read()).hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: arrays (name -> array, rows along the first axis) as path/<name>.npy in float64.  Beyond 64 MB in all,
+    every array keeps the same share of its rows, picked by a fixed seed (the same rows for the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and len(a) > 1:
+            keep = int(len(a) * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 class GridRun(object):
@@ -455,8 +489,13 @@ def grid_mode(args, torch, dist, dev, world, rank, local_rank):
     per_rank = per_rank_breakdown([kern_ms, exchange['gather_ms'], exchange['unpermute_ms'], exchange['d2h_ms'], len(run.idx),
                                    run.info['launches']], dev) if (world > 1 or args.force_collective) else None
     devices_seen = rank_devices(torch, dist, dev) if (world > 1 or args.force_collective) else None
-    run.poisoned_step()                                    # untimed; the parity check below reads this step's output
-    res, res_ij = run.results() if rank == 0 else (None, None)
+    if args.dump_outputs and rank == 0:
+        out, ij = run.results()                            # the last timed step's results, as the host receives them
+        dump_outputs(args.dump_outputs, {'results': out, 'peak_index': ij})
+    res = res_ij = None
+    if args.full:
+        run.poisoned_step()                                # untimed; the parity check below reads this step's output
+        res, res_ij = run.results() if rank == 0 else (None, None)
     n_total, info, g = run.n_total, run.info, run.g
     zero_copy, device_unpermute = getattr(run.gather, 'zero_copy', False), getattr(run.gather, 'device_unpermute', False)
     import numpy as _np
@@ -464,7 +503,7 @@ def grid_mode(args, torch, dist, dev, world, rank, local_rank):
     run.close()
 
     weak = None
-    if world > 1 and args.scaling == 'strong' and not args.no_weak:
+    if args.full and world > 1 and args.scaling == 'strong' and not args.no_weak:
         wrun = GridRun(args, dev, world, rank, local_rank, t1, t2, args.grid * world, angles, rot)
         ws = max(3, args.steps // 4)
         w_el, _ = timed_steps(torch, dist, world, wrun, ws, 1)
@@ -520,6 +559,8 @@ def grid_mode(args, torch, dist, dev, world, rank, local_rank):
         },
         'setup_s': {'generate_and_upload_pair': t_gen},
     }
+    if not args.full:
+        del line['config']['parity_reads']
     if weak is not None:
         line['weak_scaling'] = weak
     if rebalanced is not None:
@@ -547,14 +588,14 @@ def grid_mode(args, torch, dist, dev, world, rank, local_rank):
     # The reference's DEFAULT configuration is timed HERE, straight after the headline's steps and before the CPU baselines:
     # behind ~12 s of 16-core host work with the GPU idle its steps read 0.5 ms above their own kernel time (round 4's
     # driver run); its oracle comparison follows after the baselines.
-    also_defaults = world == 1 and not args.no_also_defaults and not args.force_collective and args.img_size == 34 and args.angles == 7
+    also_defaults = args.full and world == 1 and not args.no_also_defaults and not args.force_collective and args.img_size == 34 and args.angles == 7
     defaults_run = defaults_timed(args, torch, dist, dev, local_rank, t1, t2) if also_defaults else None
-    if world == 1 and not args.force_collective and not args.no_seam:
+    if args.full and world == 1 and not args.force_collective and not args.no_seam:
         line['seam_inclusive'] = seam_inclusive(args, img1, img2, g, s, angles, rot, local_rank, res, res_ij)
     oracle_run = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line['cpu_baseline'], oracle_run = cpu_baselines(args, img1, img2, g, n_total, angles, rot, s)
-    if args.check > 0 or oracle_run is not None:
+    if args.full and (args.check > 0 or oracle_run is not None):
         line['parity_check'] = parity_block(args, img1, img2, g, n_total, res, res_ij, angles, rot, s, oracle_run)
         if 'fft_f32_differential' in line.get('cpu_baseline', {}):
             # how far a float32-FFT matcher (OpenCV's route, unpinnable here) parts from the exact-integer specification
@@ -683,25 +724,33 @@ def stream_mode(args, torch, dist, dev, world, rank, local_rank):
 
     run = Run()
     elapsed, kern_first_ms = timed_steps(torch, dist, world, run, args.steps, args.warmup)
-    # the kernels of ONE pair in steady state: both slots uploaded, nothing for the launches to wait for (the events around
-    # the first pair of a step also hold that pair's wait for its own upload - reported as kernel_ms_first_pair_incl_upload_wait)
-    ctx.sync()
-    torch.cuda.synchronize()
-    ka, kb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ctx.run()
-    ka.record()
-    for _ in range(3):
+    if args.dump_outputs and rank == 0:
+        # the pairs the last timed step kept on the host (this rank's first three), as the host received them
+        arrays = {}
+        for p in sorted(keep & set(results)):
+            arrays['pair%d_results' % p], arrays['pair%d_peak_index' % p] = results[p]
+        dump_outputs(args.dump_outputs, arrays)
+    kern_ms = None
+    if args.full:
+        # the kernels of ONE pair in steady state: both slots uploaded, nothing for the launches to wait for (the events around
+        # the first pair of a step also hold that pair's wait for its own upload - reported as kernel_ms_first_pair_incl_upload_wait)
+        ctx.sync()
+        torch.cuda.synchronize()
+        ka, kb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ctx.run()
-    kb.record()
-    kb.synchronize()
-    ctx.check()
-    kern_ms = ka.elapsed_time(kb) / 3.0
+        ka.record()
+        for _ in range(3):
+            ctx.run()
+        kb.record()
+        kb.synchronize()
+        ctx.check()
+        kern_ms = ka.elapsed_time(kb) / 3.0
     from sea_ice_drift_amd.dist import per_rank_breakdown
     per_rank = per_rank_breakdown([timed_steps.local_elapsed / args.steps * 1e3, kern_first_ms, len(mine)], dev) if world > 1 else None
     line = None
     # parity: up to three pairs of this rank against the oracle on a subsample (checker only)
     ok, checked = True, 0
-    if args.check > 0 and mine:
+    if args.full and args.check > 0 and mine:
         from oracle import c_oracle
         c_oracle.build()
         sel = np.random.default_rng(1).choice(n_pts, size=min(args.check, n_pts), replace=False)
@@ -713,7 +762,7 @@ def stream_mode(args, torch, dist, dev, world, rank, local_rank):
             ok = ok and (np.array_equal(got_ij[sel], exp_ij) and np.array_equal(got[sel, :4], exp[:, :4], equal_nan=True)
                          and np.allclose(got[sel, 4], exp[:, 4], rtol=1e-5, atol=1e-5, equal_nan=True))
             checked += 1
-    if world > 1:
+    if args.full and world > 1:
         flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         ok = bool(flag.item())
@@ -732,15 +781,17 @@ def stream_mode(args, torch, dist, dev, world, rank, local_rank):
                        'pairs_total': args.pairs, 'pairs_per_gpu': len(mine), 'points_per_pair': int(n_pts),
                        'ms_per_pair': elapsed / args.steps * 1e3 / max(len(mine), 1),
                        'parallelism': 'pairs dealt round-robin to %d GPU(s); no collective on the data path' % world},
-            'roofline': {'bound': 'mfma', 'achieved': 2.0 * info['macs'] / (kern_ms * 1e-3) / 1e12, 'peak': MFMA_I8_PEAK_TOPS,
-                         'unit': 'TFLOP/s', 'frac': 2.0 * info['macs'] / (kern_ms * 1e-3) / 1e12 / MFMA_I8_PEAK_TOPS,
-                         'traffic': None, 'kernel_ms_per_pair': kern_ms, 'kernel_ms_first_pair_incl_upload_wait': kern_first_ms,
-                         'note': 'kernels of one pair in steady state (HIP events on the launch stream around 3 runs on a resident pair after the '
-                                 'timed steps: nothing to wait for); the step time also holds the 200 MB H2D upload of every pair, overlapped - '
-                                 'ms_per_pair above is the streaming rate, bound by the uploads when they take longer than the kernels'},
-            'parity_check': {'pairs_checked_per_rank': checked, 'ok': ok},
             'setup_s': {'generate_and_pin_pairs': t_gen},
         }
+        if args.full:
+            line['roofline'] = {
+                'bound': 'mfma', 'achieved': 2.0 * info['macs'] / (kern_ms * 1e-3) / 1e12, 'peak': MFMA_I8_PEAK_TOPS,
+                'unit': 'TFLOP/s', 'frac': 2.0 * info['macs'] / (kern_ms * 1e-3) / 1e12 / MFMA_I8_PEAK_TOPS,
+                'traffic': None, 'kernel_ms_per_pair': kern_ms, 'kernel_ms_first_pair_incl_upload_wait': kern_first_ms,
+                'note': 'kernels of one pair in steady state (HIP events on the launch stream around 3 runs on a resident pair after the '
+                        'timed steps: nothing to wait for); the step time also holds the 200 MB H2D upload of every pair, overlapped - '
+                        'ms_per_pair above is the streaming rate, bound by the uploads when they take longer than the kernels'}
+            line['parity_check'] = {'pairs_checked_per_rank': checked, 'ok': ok}
         if per_rank is not None:                               # every rank's own clock: the slowest one is named
             line['step_breakdown_ms'] = {'per_rank': {'batch_ms': [float(v) for v in per_rank[:, 0]],
                                                       'kernel_ms_first_pair': [float(v) for v in per_rank[:, 1]],
@@ -786,6 +837,10 @@ def ftpm_mode(args, torch, dist, dev, world, rank, local_rank):
         if k >= args.warmup:
             t_ft.append(t1 - t0)
             t_pm.append(t2 - t1)
+    if args.dump_outputs:                                   # what the two public calls returned in the last timed step
+        dump_outputs(args.dump_outputs, {'u': u, 'v': v, 'a': a, 'r': r, 'h': h, 'lon2': lon2, 'lat2': lat2,
+                                         'ft_u': uft, 'ft_v': vft, 'ft_lon1': lon1ft, 'ft_lat1': lat1ft,
+                                         'ft_lon2': lon2ft, 'ft_lat2': lat2ft})
     ft_s, pm_s = float(np.mean(t_ft)), float(np.mean(t_pm))
     ok = np.isfinite(u)
     # feature-tracking vectors against the synthetic displacement field
@@ -809,7 +864,7 @@ def ftpm_mode(args, torch, dist, dev, world, rank, local_rank):
         'detector': 'sea_ice_drift_amd.orb (own ORB-family specification behind the reference interface; OpenCV parity unpinned)',
         'setup_s': {'generate_pair': t_gen},
     }
-    if args.check > 0:
+    if args.full and args.check > 0:
         # PM on the FT-derived first guess against the C oracle: the same prelude (first guess, search border, validity
         # mask) feeds both; compared are a, r (bit-exact), h (1e-5) and the destination lon/lat (bit-exact)
         from oracle import c_oracle

@@ -75,8 +75,8 @@ def test_config1_standin_50x50_grid_on_4000px_pair(c_oracle):
 
 def test_config3_dry_run_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher and WORLD_SIZE unset: strong scaling on the same grid."""
-    one = run_bench('--gpus', '1', '--steps', '3', '--warmup', '1', '--size', '3000', '--grid', '60', '--no-cpu-baseline')
-    two = run_bench('--gpus', '2', '--steps', '3', '--warmup', '1', '--size', '3000', '--grid', '60', '--no-cpu-baseline')
+    one = run_bench('--gpus', '1', '--steps', '3', '--warmup', '1', '--size', '3000', '--grid', '60', '--full', '--no-cpu-baseline')
+    two = run_bench('--gpus', '2', '--steps', '3', '--warmup', '1', '--size', '3000', '--grid', '60', '--full', '--no-cpu-baseline')
     assert one['n_gpus'] == 1 and two['n_gpus'] == 2
     assert two['scaling'] == 'strong' and two['config']['points_total'] == one['config']['points_total'] == 3600
     assert sum(two['config']['points_per_gpu_all']) == 3600 and len(two['config']['points_per_gpu_all']) == 2
@@ -101,12 +101,32 @@ def test_config3_dry_run_bench_spawns_its_own_ranks():
     assert 'rebalance' not in one['config']
 
 
+def test_plain_bench_line_and_dumped_outputs(tmp_path, c_oracle):
+    """A plain run (no --full) prints the headline line alone; --dump-outputs writes what the last timed step returned to the
+    host, and that equals the C oracle on every point of the grid."""
+    d = run_bench('--gpus', '1', '--steps', '2', '--warmup', '1', '--size', '3000', '--grid', '60', '--dump-outputs', str(tmp_path))
+    assert d['steps'] == 2 and d['ms_per_step'] > 0 and d['value'] > 0 and d['unit'] == 'grid-points/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'u8' and d['metric'].startswith('PM grid-points/sec')
+    assert not {'cpu_baseline', 'parity_check', 'reference_defaults', 'seam_inclusive', 'weak_scaling'} & set(d)
+    out, ij = np.load(str(tmp_path / 'results.npy')), np.load(str(tmp_path / 'peak_index.npy'))
+    assert out.dtype == ij.dtype == np.float64 and out.shape == (3600, 5) and ij.shape == (3600, 3)
+    img1, img2 = syn.make_pair(3000, 3000)
+    g = syn.make_grid(3000, 3000, (60, 60), border='mixed')
+    angles = list(range(-7, 8))
+    exp, exp_ij = c_oracle.pm_batch(img1, img2, g['c1'], g['r1'], g['c2fg'], g['r2fg'], g['border'], 34, 0.0, angles,
+                                    rot=my.rotation_table(angles, 0.0, 34), nthreads=8)
+    np.testing.assert_array_equal(ij, exp_ij)
+    np.testing.assert_array_equal(out[:, :4], exp[:, :4])
+    np.testing.assert_allclose(out[:, 4], exp[:, 4], rtol=1e-5, atol=1e-5, equal_nan=True)
+    assert np.isfinite(out[:, 0]).sum() > 3000
+
+
 def test_config5_dry_run_two_ranks_stream_their_shares():
     """BASELINE config 5's multi-GPU half as a dry run: `python bench.py --mode stream --gpus 2` - two ranks sharing the
     one GPU (gloo for the flag reduction), each streaming its share of the batch through its own two device slots; no
     collective on the data path.  Every rank's pairs are checked against the oracle and every rank's clock is reported."""
     d = run_bench('--mode', 'stream', '--gpus', '2', '--pairs', '6', '--steps', '1', '--warmup', '1', '--size', '3000', '--grid', '60',
-                  '--check', '32', timeout=1800)
+                  '--full', '--check', '32', timeout=1800)
     assert d['n_gpus'] == 2 and d['config']['pairs_total'] == 6 and d['config']['pairs_per_gpu'] == 3
     assert d['parity_check']['ok'] and d['parity_check']['pairs_checked_per_rank'] == 3
     pr = d['step_breakdown_ms']['per_rank']
@@ -120,7 +140,7 @@ def test_rccl_code_path_runs_on_one_gpu():
     the per-step gather of the packed result block on device tensors (dist.PackedGatherer(force_collective=True)) - the
     branch that a dry run on one GPU (gloo, two ranks sharing the device) cannot reach.  Results still equal the oracle."""
     d = run_bench('--gpus', '1', '--force-collective', '--steps', '5', '--warmup', '2', '--size', '3000', '--grid', '60',
-                  '--no-cpu-baseline')
+                  '--full', '--no-cpu-baseline')
     bd = d['step_breakdown_ms']
     assert bd['backend'] == 'nccl'
     # one kernel (sid_pm_unpermute) reads the gathered block and writes the pinned host buffer: no separate copy
@@ -133,7 +153,7 @@ def test_config4_ft_feeding_pm_on_the_full_size_pair():
     """BASELINE config 4 (ftlib.py:236-281 feeding seaicedrift.py:62-88): get_drift_FT with the GPU detector and matcher ->
     get_drift_PM on the 10000x10000 pair.  >= 99 % of the feature-tracking vectors lie within 3 px of the synthetic
     displacement field, and the PM result on the FT-derived first guess equals the C oracle on a 400-point subsample."""
-    d = run_bench('--mode', 'ftpm', '--steps', '2', '--warmup', '1', '--check', '400', timeout=2400)
+    d = run_bench('--mode', 'ftpm', '--steps', '2', '--warmup', '1', '--full', '--check', '400', timeout=2400)
     assert d['ft_vectors'] > 10000 and d['ft_vectors_within_3px_of_truth'] >= 0.99
     assert d['parity_check']['ok'] and d['parity_check']['points'] == 400
     assert d['valid_grid_points'] > 35000 and d['median_abs_drift_error_px'] < 4.0
@@ -142,7 +162,7 @@ def test_config4_ft_feeding_pm_on_the_full_size_pair():
 
 def test_config5_stream_16_pairs_full_size():
     """16 pairs of 10000x10000 px streamed through the two device slots; 3 pairs checked against the oracle."""
-    d = run_bench('--mode', 'stream', '--pairs', '16', '--steps', '1', '--warmup', '1', '--check', '32', timeout=2400)
+    d = run_bench('--mode', 'stream', '--pairs', '16', '--steps', '1', '--warmup', '1', '--full', '--check', '32', timeout=2400)
     assert d['config']['pairs_total'] == 16 and d['config']['pairs_per_gpu'] == 16
     assert d['parity_check']['ok'] and d['parity_check']['pairs_checked_per_rank'] == 3
     assert d['value'] > 0 and d['config']['points_per_pair'] == 40000

@@ -4,8 +4,8 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; OUT=$R/gpurun_out/r06_last; mkdir -p $OUT; cd $R
 timeout 1500 python3 -m pytest tests -m gpu -q 2>&1 | tail -8 > $OUT/pytest_gpu.txt
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc FETCH_SIZE -d /tmp/lf -o pf -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE -d /tmp/lw -o pw -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE -d /tmp/lf -o pf -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE -d /tmp/lw -o pw -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
 python3 $R/tools/pmc_traffic.py $(find /tmp/lf -name "*.db" | head -1) $(find /tmp/lw -name "*.db" | head -1) pm_kernel > $OUT/pmc_traffic.json
 python3 - "$OUT/pmc_traffic.json" "$R" > $OUT/traffic.json <<'PY'
 import hashlib, json, sys
@@ -20,6 +20,6 @@ old.update({'so_md5': hashlib.md5(open(root + '/sea_ice_drift_amd/libsid_pm.so',
 print(json.dumps(old, indent=1))
 PY
 cd $R && cp $OUT/traffic.json profiles/traffic.json
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/pytest_gpu.txt; python3 -c "
 import json; d = json.load(open('$OUT/bench.json')); print(d['ms_per_step'], d['roofline']['frac'], d['roofline']['traffic'], d['roofline']['traffic_note'][:120])"

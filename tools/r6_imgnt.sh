@@ -6,8 +6,8 @@ AB_ROUNDS=2 bash tools/r6_ab.sh r06_imgnt sea_ice_drift_amd/libsid_pm.so build/a
 cd /tmp && export TMPDIR=/tmp
 for v in base imgnt; do
   if [ $v = imgnt ]; then export SID_PM_LIB=$R/build/ab/lib_imgnt.so; else unset SID_PM_LIB; fi
-  rocprofv3 --pmc FETCH_SIZE -d /tmp/nf_$v -o pf -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
-  rocprofv3 --pmc WRITE_SIZE -d /tmp/nw_$v -o pw -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
+  rocprofv3 --pmc FETCH_SIZE -d /tmp/nf_$v -o pf -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
+  rocprofv3 --pmc WRITE_SIZE -d /tmp/nw_$v -o pw -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-also-defaults --no-seam --check 0 > /dev/null 2>&1
   python3 $R/tools/pmc_traffic.py $(find /tmp/nf_$v -name "*.db" | head -1) $(find /tmp/nw_$v -name "*.db" | head -1) pm_kernel > $OUT/pmc_traffic_$v.json
   python3 -c "
 import json
