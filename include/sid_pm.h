@@ -26,7 +26,12 @@
  * Errors: functions return SID_PM_OK (0) or a negative code; sid_pm_last_error() gives a
  * thread-local message.  Per-point failure is never an error: exactly like the reference
  * (pmlib.py:152-154) a point whose rotated template touches a 0 pixel yields NaN x 5
- * (and -1 in out_ij); so does a search window that is not wholly inside image 2.
+ * (and -1 in out_ij).  The search window is cut from image 2 as the reference's NumPy slice
+ * cuts it (pmlib.py:200-202): an end past the last row or column is clipped to the image and the
+ * displacement is measured from the clipped shape (such points run the large-window pipeline,
+ * which takes any rectangle).  A point yields NaN x 5 (and -1) where the
+ * reference raises instead: a window that starts at row or column -1 or before (truncated as
+ * Python's int() does), or one that leaves fewer than img_size + 1 rows or columns.
  *
  * Numerics: see DESIGN.md "NCC specification".  Integer outputs (peak row/col, angle
  * index) are exact; r is the float32 the specification defines; h is float32 arithmetic
@@ -41,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SID_PM_ABI_VERSION 4
+#define SID_PM_ABI_VERSION 5
 
 /* return codes */
 #define SID_PM_OK               0
@@ -247,7 +252,10 @@ int sid_pm_get_hessian(int device, const float *ccm, int64_t rows, int64_t cols,
 /* Intermediate results of one point: rotated templates [n_angles][s][s] (uint8), the NCC
  * matrix of the winning angle and its raw Hessian magnitude [rh][rw] (float32, caller
  * provides capacity `cap` floats each), shape in rh_rw[2]; phase_cycles = shader-clock stamps at
- * the kernel's phase boundaries (one workgroup on an idle device).  Any output pointer may be NULL. */
+ * the kernel's phase boundaries (one workgroup on an idle device).  Any output pointer may be NULL.
+ * It runs the one-point kernels, which do not take a search window clipped by the bottom / right
+ * edge of image 2: such a point is SID_PM_ERR_UNSUPPORTED here (sid_pm_run and sid_pm_batch run
+ * it through the large-window pipeline). */
 int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double c2fg, double r2fg,
                        double border, int img_size, double alpha0, const double *angles,
                        const double *rot, int n_angles, uint32_t flags,

@@ -585,12 +585,14 @@ static void use_mcc_ws(sid_ws *w, const uint8_t *img1, int64_t rows1, int64_t co
 {
     const int hws = (int)((double)s / 2.);
     /* Python int(): truncation toward zero (pmlib.py:201-202) */
-    const int64_t r0 = (int64_t)(r2fg - hws - border), r1e = (int64_t)(r2fg + hws + border + 1);
-    const int64_t c0 = (int64_t)(c2fg - hws - border), c1e = (int64_t)(c2fg + hws + border + 1);
+    const int64_t r0 = (int64_t)(r2fg - hws - border), r1e_ = (int64_t)(r2fg + hws + border + 1);
+    const int64_t c0 = (int64_t)(c2fg - hws - border), c1e_ = (int64_t)(c2fg + hws + border + 1);
+    /* NumPy slicing clips an end past the image; a start of -1 or less stays NaN (NumPy wraps it, the reference raises) */
+    const int64_t r1e = r1e_ < rows2 ? r1e_ : rows2, c1e = c1e_ < cols2 ? c1e_ : cols2;
     for (int k = 0; k < 5; ++k) out5[k] = NAN;
     if (ij3) { ij3[0] = ij3[1] = ij3[2] = -1; }
     if (gap) *gap = NAN;
-    if (!(r0 >= 0 && c0 >= 0 && r1e <= rows2 && c1e <= cols2 && r1e - r0 >= s + 1 && c1e - c0 >= s + 1)) return;
+    if (!(r0 >= 0 && c0 >= 0 && r1e - r0 >= s + 1 && c1e - c0 >= s + 1)) return;
     const int wh = (int)(r1e - r0), ww = (int)(c1e - c0);
     double ddrc[2]; float rr, hh; int iyx[2];
     const int best_k = rotate_and_match_ws(w, img1, rows1, cols1, stride1, img2 + r0 * stride2 + c0, wh, ww, stride2, c1, r1,

@@ -16,7 +16,7 @@ HES_SMTH = 2
 MCC_NORM = 4
 ROT_ORDER1 = 8          # rot_order=1: bilinear template sampling (include/sid_pm.h)
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # every symbol include/sid_pm.h declares
 SYMBOLS = (

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <new>
 #include <numeric>
 #include <string>
@@ -246,16 +247,19 @@ int blocks_per_cu(int lds)
 }
 
 bool window_dims(double c2fg, double r2fg, double border, int s, int64_t rows2, int64_t cols2,
-                 int &wh, int &ww)
+                 int &wh, int &ww, bool *clipped = nullptr)
 {
     const int hws = (int)((double)s / 2.0);
     const double r0d = r2fg - hws - border, r1d = r2fg + hws + border + 1;
     const double c0d = c2fg - hws - border, c1d = c2fg + hws + border + 1;
     if (!(fabs(r0d) < 1e15 && fabs(r1d) < 1e15 && fabs(c0d) < 1e15 && fabs(c1d) < 1e15)) return false;
-    const int64_t r0 = (int64_t)r0d, r1e = (int64_t)r1d, c0 = (int64_t)c0d, c1e = (int64_t)c1d;
-    if (!(r0 >= 0 && c0 >= 0 && r1e <= rows2 && c1e <= cols2 && r1e - r0 >= s + 1 && c1e - c0 >= s + 1))
+    // NumPy slicing (pmlib.py:200-202): an end past the image is clipped to it; a start of -1 or less is not
+    // (NumPy would wrap it and the reference raises), nor is a window that leaves fewer than s + 1 rows or columns
+    const int64_t r0 = (int64_t)r0d, r1e = std::min((int64_t)r1d, rows2), c0 = (int64_t)c0d, c1e = std::min((int64_t)c1d, cols2);
+    if (!(r0 >= 0 && c0 >= 0 && r1e - r0 >= s + 1 && c1e - c0 >= s + 1))
         return false;
     wh = (int)(r1e - r0); ww = (int)(c1e - c0);
+    if (clipped) *clipped = (int64_t)r1d > rows2 || (int64_t)c1d > cols2;
     return true;
 }
 
@@ -494,13 +498,33 @@ int classify_points(sid_pm_ctx *ctx)
     }
     double macs = 0, bytes = 0, valid = 0;
     int lds_max = lds_min;
+    std::map<std::pair<int, int>, int> clipped_shape;                // windows clipped by the edge of image 2: (wh, ww) -> shape
     std::vector<int32_t> shape_of((size_t)n, 0);                      // shape of every point (0: its window does not lie inside image 2)
     for (int64_t i = 0; i < n; ++i) {
         int wh = 0, ww = 0;
-        if (!window_dims(c2fg[i], r2fg[i], border[i], s, rows2, cols2, wh, ww)) { shapes[0].idx.push_back((int32_t)i); continue; }
+        bool clipped = false;
+        if (!window_dims(c2fg[i], r2fg[i], border[i], s, rows2, cols2, wh, ww, &clipped)) { shapes[0].idx.push_back((int32_t)i); continue; }
         if (wh > 65535 || ww > 4000000) return fail(SID_PM_ERR_UNSUPPORTED, "point %lld: search window %dx%d too large (65535 rows: a launch dimension of the large-window pipeline)", (long long)i, wh, ww);
-        int k = find_shape(wh, ww);
-        if (k < 0) {
+        // a window clipped by the bottom / right edge of image 2 (NumPy slicing) has a shape the one-point kernels' layouts were
+        // not validated for (as few as two placement rows or columns next to a full-width other axis): such points run the
+        // large-window pipeline, whose kernels take any rectangle byte by byte (the benchmark grid never reaches an edge)
+        // (one shape per clipped wh x ww, kept apart from the one-point kernels' shapes of the same size; the pipeline itself runs
+        // all of its points as one batch of launches - run_large_points)
+        int k = -1;
+        if (clipped) {
+            const auto it = clipped_shape.find(std::make_pair(wh, ww));
+            if (it != clipped_shape.end()) k = it->second;
+        } else {
+            k = find_shape(wh, ww);
+        }
+        if (clipped && k < 0) {
+            Shape sh{wh, ww, 0, 4, 0, 0, 0, 0.0, {}};
+            sh.large = true;
+            sh.work = (double)(wh - s + 1) * (double)(ww - s + 1);
+            k = (int)shapes.size();
+            clipped_shape.emplace(std::make_pair(wh, ww), k);
+            shapes.push_back(sh);
+        } else if (k < 0) {
             Shape sh{wh, ww, 0, 4, 0, 0, 0, 0.0, {}};
             ShapeClass sc{false, 4, 1, 0, 0};
             if (small_ok) sc = shape_class(rp, rpp, wh, ww, s, K, flags, band8_ok, no_fixed_pitch);
@@ -1379,8 +1403,13 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
     const bool rp = use_rp(s, K);
     const int rpp = rp ? rp_paired(K) : 0;
     int wh = 0, ww = 0, lds = lds_need(rp, rpp, s + 1, s + 1, s, K, flags);
-    if (window_dims(c2fg, r2fg, border, s, ctx->cur[1].rows, ctx->cur[1].cols, wh, ww))
+    bool clipped = false;
+    if (window_dims(c2fg, r2fg, border, s, ctx->cur[1].rows, ctx->cur[1].cols, wh, ww, &clipped))
         lds = lds_need(rp, rpp, wh, ww, s, K, flags);
+    // (the one-point kernels do not take windows clipped by the edge of image 2: the batch entry points run them through the
+    // large-window pipeline - classify_points)
+    if (clipped) return fail(SID_PM_ERR_UNSUPPORTED, "debug_point: the search window is clipped by the edge of image 2 (%dx%d); "
+                                                     "sid_pm_run / sid_pm_batch take such points", wh, ww);
     if (lds > sid::max_lds_bytes()) return fail(SID_PM_ERR_UNSUPPORTED, "search window too large for LDS");
     (void)alpha0;
     if (!sid::mfma_img_size_supported(s)) return fail(SID_PM_ERR_UNSUPPORTED, "debug_point: template sides 2..64 (sid_pm_rotate_and_match returns the matrix and the template of any size)");

@@ -1645,6 +1645,8 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
     const double r0d = r2fg - hws - border, r1d = r2fg + hws + border + 1;
     const double c0d = c2fg - hws - border, c1d = c2fg + hws + border + 1;
     const bool finite = fabs(r0d) < 1e15 && fabs(r1d) < 1e15 && fabs(c0d) < 1e15 && fabs(c1d) < 1e15;
+    // (windows that NumPy slicing would clip at the bottom / right of image 2 never come here: pm_capi.hip classify_points sends
+    // them to the large-window pipeline and debug_point refuses them - this kernel keeps rejecting them as a safety net)
     const int64_t r0 = finite ? (int64_t)r0d : -1, r1e = finite ? (int64_t)r1d : -1;
     const int64_t c0 = finite ? (int64_t)c0d : -1, c1e = finite ? (int64_t)c1d : -1;
     const bool inside = finite && r0 >= 0 && c0 >= 0 && r1e <= A.rows2 && c1e <= A.cols2 &&

@@ -20,6 +20,12 @@ them, with a sha256) and the outputs the reference's functions returned:
   g8_rotate_and_match.npz  pmlib.rotate_and_match called directly (pmlib.py:117-174) - the shape of the reference's own test
                      (tests.py:336-337: whole image 2 as the window, img_size=50, 7 angles), rectangular windows, img_size up to
                      128 - and pmlib.use_mcc with search borders of 112 / 160 / 250 px; the NCC matrices as sha256 + a subsample
+  g9_edges.npz       pmlib.use_mcc at the edges of the images: search windows flush with each edge and corner of image 2, clipped
+                     at the bottom / right as NumPy clips a slice (pmlib.py:200-202; the displacement then comes from the clipped
+                     shape), clipped down to img_size + 1 rows / columns, fractional starts in (-1, 0); templates whose footprint
+                     is inside image 1 but whose bounding box reaches its edges; the points where the reference raises instead
+                     (start -1, img_size rows / columns left) by name and exception type.  Two odd-sized pairs, img1 and img2 of
+                     different shapes; restated matcher injected as in G3
   g4_pattern_matching.npz  pmlib.pattern_matching    (pmlib.py:326-497) end to end on an
                      affine stand-in for Nansat, incl. the kernel-input vectors it built
   g5_fullsize.npz    sha256 of the 10000x10000 benchmark pair + C-oracle results on a 1 %
@@ -29,7 +35,7 @@ them, with a sha256) and the outputs the reference's functions returned:
   g7_feature_tracking.npz  ftlib.feature_tracking    (ftlib.py:241-285: domain, Lowe, drift and least-squares
                      filters) on synthetic key points / descriptors, brute-force matcher injected
 
-    python tests/golden/make_golden.py [g1 g2 g3 g4 g5]
+    python tests/golden/make_golden.py [g1 g2 g3 g4 g5 ... g9]
 """
 import os
 import sys
@@ -176,6 +182,132 @@ def make_g3c(pmlib):
                                     for i in range(len(c1))], dtype=np.float64)
                     d['out_s%d_a%d_k%d_o%d' % (s, ai, k, order)] = res
     np.savez_compressed(os.path.join(HERE, 'g3c_large_rotations.npz'), **d)
+
+
+# ---------------------------------------------------------------- G9: edges
+G9_PAIRS = ((901, (301, 299), (290, 413)), (902, (283, 411), (307, 297)))   # seed, img1 shape, img2 shape
+G9_VARIANTS = ((34, 0.0, 0), (34, 0.0, 1), (35, -3.85, 0), (35, -3.85, 1))   # img_size, alpha0, rot_order
+G9_ANGLES = [-3, 0, 3]
+G9_BORDERS = (20, 50)
+
+
+def g9_pair(k):
+    """Pair k of G9: cut from one seeded pair (same origin, so that points match), shapes of G9_PAIRS."""
+    seed, sh1, sh2 = G9_PAIRS[k]
+    a, b = syn.make_pair(max(sh1[0], sh2[0]), max(sh1[1], sh2[1]), seed=seed)
+    return np.ascontiguousarray(a[:sh1[0], :sh1[1]]), np.ascontiguousarray(b[:sh2[0], :sh2[1]])
+
+
+def template_inside(img1, c1, r1, s, alpha0, angles, rot_order):
+    """No sample of the rotated templates reads a 0 (outside the image: cval 0) - the reference's template test, pmlib.py:152
+    (rot_order 2..5 are scanned with their bilinear footprint: the search positions only have to lie near the edges)."""
+    get = po.get_template_order1 if rot_order >= 1 else po.get_template
+    return all(get(img1, c1, r1, a - alpha0, s).min() > 0 for a in angles)
+
+
+def edge_centres(img1, s, alpha0, angles, rot_order):
+    """Template centres of image 1 flush with its edges: the outermost centre on a 0.25 px lattice whose templates are still
+    inside - top, bottom, left, right and the four corners (their bounding boxes reach the first / last row and column)."""
+    rows1, cols1 = img1.shape
+    ok = lambda c, r: template_inside(img1, c, r, s, alpha0, angles, rot_order)
+    mid_c, mid_r = cols1 / 2.0 + 0.25, rows1 / 2.0 - 0.25
+
+    def scan(start, step, fn):
+        v = start
+        while not fn(v):
+            v += step
+        return v
+    top = scan(0.0, 0.25, lambda r: ok(mid_c, r))
+    bottom = scan(rows1 - 1.0, -0.25, lambda r: ok(mid_c, r))
+    left = scan(0.0, 0.25, lambda c: ok(c, mid_r))
+    right = scan(cols1 - 1.0, -0.25, lambda c: ok(c, mid_r))
+    out = {'top': (mid_c, top), 'bottom': (mid_c, bottom), 'left': (left, mid_r), 'right': (right, mid_r)}
+    for name, (c, r) in (('tl', (left, top)), ('tr', (right, top)), ('bl', (left, bottom)), ('br', (right, bottom))):
+        dc, dr = (0.25 if c == left else -0.25), (0.25 if r == top else -0.25)
+        while not ok(c, r):
+            c, r = c + dc, r + dr
+        out[name] = (c, r)
+    return out
+
+
+def g9_points(img1, img2, s, alpha0, angles, rot_order, borders=G9_BORDERS):
+    """(names, c1, r1, c2fg, r2fg, border, raises) of the edge cases of one pair.  `raises`: the cases where the reference raises
+    (NaN in the kernel and the oracles).  Windows: r0 = int(r2fg - hws - b), r1e = min(int(r2fg + hws + b + 1), rows2)."""
+    rows1, cols1 = img1.shape
+    rows2, cols2 = img2.shape
+    hws = int(s / 2.)
+    names, pts, raises = [], [], []
+
+    def add(name, c1, r1, c2, r2, b, raising=False):
+        names.append(name)
+        pts.append((c1, r1, c2, r2, b))
+        raises.append(raising)
+
+    def centre1(c2, r2):                                   # a template centre of image 1 near the window's, inside image 1
+        m = hws + 10
+        return float(np.clip(c2 + 1.25, m, cols1 - 1 - m)), float(np.clip(r2 - 0.75, m, rows1 - 1 - m))
+
+    for b in borders:
+        lo = hws + b                                       # r2fg of a window whose first row is row 0
+        hi_r, hi_c = rows2 - hws - b - 1, cols2 - hws - b - 1   # ... whose last row / column is the image's last
+        mid_r, mid_c = rows2 // 2, cols2 // 2
+        win = {'top': (mid_c, lo), 'bottom': (mid_c, hi_r), 'left': (lo, mid_r), 'right': (hi_c, mid_r),
+               'tl': (lo, lo), 'tr': (hi_c, lo), 'bl': (lo, hi_r), 'br': (hi_c, hi_r)}
+        for k, (c2, r2) in win.items():
+            add('b%d_flush_%s' % (b, k), *centre1(c2, r2), c2, r2, b)
+        for k in (1, 2, 3, 4, b - 3):
+            add('b%d_clip%d_bottom' % (b, k), *centre1(mid_c, hi_r + k), mid_c, hi_r + k, b)
+            add('b%d_clip%d_right' % (b, k), *centre1(hi_c + k, mid_r), hi_c + k, mid_r, b)
+            add('b%d_clip%d_both' % (b, k), *centre1(hi_c + k, hi_r + k), hi_c + k, hi_r + k, b)
+        # s + 1 rows / columns left after clipping (the fewest that run), then s (the reference raises)
+        rmin, cmin = rows2 - s - 1 + lo, cols2 - s - 1 + lo
+        add('b%d_min_rows' % b, *centre1(mid_c, rmin), mid_c, rmin, b)
+        add('b%d_min_cols' % b, *centre1(cmin, mid_r), cmin, mid_r, b)
+        add('b%d_min_both' % b, *centre1(cmin, rmin), cmin, rmin, b)
+        add('b%d_raise_rows_s' % b, *centre1(mid_c, rmin + 1), mid_c, rmin + 1, b, True)
+        add('b%d_raise_cols_s' % b, *centre1(cmin + 1, mid_r), cmin + 1, mid_r, b, True)
+        # fractional starts in (-1, 0): int() truncates them to 0
+        for f in (0.5, 0.999):
+            add('b%d_frac%g_top' % (b, f), *centre1(mid_c, lo - f), mid_c, lo - f, b)
+            add('b%d_frac%g_left' % (b, f), *centre1(lo - f, mid_r), lo - f, mid_r, b)
+        add('b%d_frac_tl_clip_br' % b, *centre1(lo - 0.25, lo - 0.75), lo - 0.25, lo - 0.75, b)
+        # a start of -1: NumPy wraps the slice and the reference raises
+        add('b%d_raise_start_row' % b, *centre1(mid_c, lo - 1), mid_c, lo - 1, b, True)
+        add('b%d_raise_start_col' % b, *centre1(lo - 1, mid_r), lo - 1, mid_r, b, True)
+    # templates flush with the edges of image 1 (their bounding boxes reach its first / last row and column); windows
+    # around the same place of image 2 where it has room, clipped or flush where it does not
+    b = borders[0]
+    for k, (c1, r1) in edge_centres(img1, s, alpha0, angles, rot_order).items():
+        c2 = float(np.clip(round(c1), hws + b, cols2 + 3 - hws - b))
+        r2 = float(np.clip(round(r1), hws + b, rows2 + 3 - hws - b))
+        add('patch_%s' % k, c1, r1, c2, r2, b)
+    v = np.array(pts, dtype=np.float64)
+    return np.array(names), v[:, 0], v[:, 1], v[:, 2], v[:, 3], v[:, 4], np.array(raises)
+
+
+def make_g9(pmlib):
+    """use_mcc of the reference at the edges of the images (restated matcher injected as in G3); see g9_points."""
+    d = {}
+    for p in range(len(G9_PAIRS)):
+        img1, img2 = g9_pair(p)
+        d['pair%d_sha' % p] = syn.sha256(img1, img2)
+        for s, alpha0, order in G9_VARIANTS:
+            key = 'p%d_s%d_o%d' % (p, s, order)
+            names, c1, r1, c2fg, r2fg, border, raises = g9_points(img1, img2, s, alpha0, G9_ANGLES, order)
+            out = np.full((len(names), 5), np.nan)
+            raised = []
+            for i in range(len(names)):
+                try:
+                    out[i] = pmlib.use_mcc(c1[i], r1[i], c2fg[i], r2fg[i], border[i], img1, img2, s, alpha0,
+                                           angles=G9_ANGLES, rot_order=order, template_matcher=po.match_template)
+                except Exception as e:                     # noqa: recorded - where the reference raises, the port returns NaN
+                    raised.append('%s:%s' % (names[i], type(e).__name__))
+            assert [n.split(':')[0] for n in raised] == list(names[raises]), (key, raised)
+            d['names_' + key] = names
+            d['pts_' + key] = np.stack([c1, r1, c2fg, r2fg, border], axis=1)
+            d['out_' + key] = out
+            d['raised_' + key] = np.array(raised)
+    np.savez_compressed(os.path.join(HERE, 'g9_edges.npz'), **d)
 
 
 def g2_inputs():
@@ -472,7 +604,7 @@ def make_g7():
 
 
 def main():
-    which = sys.argv[1:] or ['g1', 'g1b', 'g1c', 'g2', 'g3', 'g3b', 'g3c', 'g3d', 'g4', 'g5', 'g6', 'g7', 'g8']
+    which = sys.argv[1:] or ['g1', 'g1b', 'g1c', 'g2', 'g3', 'g3b', 'g3c', 'g3d', 'g4', 'g5', 'g6', 'g7', 'g8', 'g9']
     if 'g7' in which:
         t = time.time()
         make_g7()
@@ -483,7 +615,7 @@ def main():
         make_g6(reflib)
         print('g6 done in %.1f s' % (time.time() - t))
     c_oracle.build()
-    for name, fn in (('g1', make_g1), ('g1b', make_g1b), ('g1c', make_g1c), ('g3d', make_g3d), ('g2', make_g2), ('g3', make_g3), ('g3b', make_g3b), ('g3c', make_g3c), ('g4', make_g4), ('g8', make_g8)):
+    for name, fn in (('g1', make_g1), ('g1b', make_g1b), ('g1c', make_g1c), ('g3d', make_g3d), ('g2', make_g2), ('g3', make_g3), ('g3b', make_g3b), ('g3c', make_g3c), ('g4', make_g4), ('g8', make_g8), ('g9', make_g9)):
         if name in which:
             t = time.time()
             fn(pmlib)

@@ -183,6 +183,45 @@ def test_out_of_image_window_is_nan(c_oracle):
     np.testing.assert_array_equal(out, exp)
 
 
+# ---------------------------------------------------------------- G9 edges
+@pytest.mark.parametrize('p', range(len(mg.G9_PAIRS)))
+def test_g9_edges_numpy_and_c(c_oracle, p):
+    """Fixture G9: the reference's use_mcc with search windows flush with / clipped by the edges of image 2 (NumPy slicing,
+    pmlib.py:200-202) and templates flush with the edges of image 1, on odd-sized pairs of unequal shapes.  Both oracle forms
+    reproduce it bit for bit, h included; where the reference raises, they return NaN (ij -1)."""
+    g = load('g9_edges.npz')
+    img1, img2 = mg.g9_pair(p)
+    assert syn.sha256(img1, img2) == str(g['pair%d_sha' % p])
+    assert img1.shape != img2.shape and all(n % 4 for n in img1.shape + img2.shape)
+    for s, alpha0, order in mg.G9_VARIANTS:
+        key = 'p%d_s%d_o%d' % (p, s, order)
+        names, c1, r1, c2fg, r2fg, border, raises = mg.g9_points(img1, img2, s, alpha0, mg.G9_ANGLES, order)
+        np.testing.assert_array_equal(names, g['names_' + key])                     # the points regenerate from the code
+        np.testing.assert_array_equal(np.stack([c1, r1, c2fg, r2fg, border], axis=1), g['pts_' + key])
+        exp = g['out_' + key]
+        raised = [str(x).split(':')[0] for x in g['raised_' + key]]
+        assert raised == list(names[raises]) and len(raised) == 8
+        assert np.isnan(exp[raises]).all() and np.isfinite(exp[~raises, :4]).all()
+        flags = 1 | (po.FLAG_ROT_ORDER1 if order else 0)
+        got_c, ij = c_oracle.pm_batch(img1, img2, c1, r1, c2fg, r2fg, border, s, alpha0, mg.G9_ANGLES,
+                                      rot=rot_for(mg.G9_ANGLES, alpha0, s), flags=flags, nthreads=4)
+        np.testing.assert_array_equal(got_c, exp, err_msg=key)                       # bit-exact incl. NaN rows and h
+        assert ((ij[:, 2] == -1) == raises).all()
+        got_n, ij_n = po.pm_batch(img1, img2, c1, r1, c2fg, r2fg, border, s, alpha0, mg.G9_ANGLES, flags=flags)
+        np.testing.assert_array_equal(got_n, exp, err_msg=key)
+        np.testing.assert_array_equal(ij_n, ij)
+        # the windows the fixture covers: clipped at the bottom / right, down to s + 1 rows / columns, flush
+        hws = s // 2
+        r0 = (r2fg - hws - border).astype(np.int64)
+        r1e = np.minimum((r2fg + hws + border + 1).astype(np.int64), img2.shape[0])
+        c1e = np.minimum((c2fg + hws + border + 1).astype(np.int64), img2.shape[1])
+        ok = ~raises
+        assert ((r2fg + hws + border + 1).astype(np.int64) > img2.shape[0])[ok].sum() >= 10
+        assert ((c2fg + hws + border + 1).astype(np.int64) > img2.shape[1])[ok].sum() >= 10
+        assert (((r1e - r0) == s + 1) & ok).any() and (r0[ok] == 0).any() and (r1e[ok] == img2.shape[0]).any()
+        assert (c1e[ok] == img2.shape[1]).any()
+
+
 def test_g5_fullsize_subsample_present():
     g = load('g5_fullsize.npz')
     assert g['out'].shape == (400, 5) and g['ij'].shape == (400, 3)
