@@ -41,6 +41,11 @@ ORB_SYMBOLS = ('sid_orb_detect', 'sid_orb_last_error', 'sid_orb_release')
 # every symbol include/sid_fg.h declares (first-guess evaluation, same library)
 FG_SYMBOLS = ('sid_fg_interp_linear', 'sid_fg_nearest_dist', 'sid_fg_distance_image', 'sid_fg_last_error', 'sid_fg_release')
 
+# every symbol include/sid_defor.h declares (deformation on a triangulation, same library)
+DEFOR_SYMBOLS = ('sid_defor_triangulation', 'sid_defor_elems', 'sid_defor_triangulation_device', 'sid_defor_elems_device',
+                 'sid_defor_debug_hypot', 'sid_defor_last_error', 'sid_defor_release')
+DEFOR_ERR_INDEX = -32   # include/sid_defor.h SID_DEFOR_ERR_INDEX
+
 _u8p = C.POINTER(C.c_uint8)
 _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
@@ -141,6 +146,15 @@ def lib():
     if hasattr(L, 'sid_fg_distance_image'):
         L.sid_fg_distance_image.argtypes = [C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int64, _f64p]
     L.sid_fg_last_error.restype = C.c_char_p
+    if hasattr(L, 'sid_defor_triangulation'):
+        vp = C.c_void_p
+        L.sid_defor_triangulation.argtypes = [C.c_int] + [_f64p] * 4 + [C.c_int64, vp, C.c_int, C.c_int64] + [_f64p] * 5
+        L.sid_defor_elems.argtypes = [C.c_int] + [_f64p] * 5 + [C.c_int64] + [_f64p] * 3
+        L.sid_defor_triangulation_device.argtypes = [vp] * 4 + [C.c_int64, vp, C.c_int, C.c_int64] + [vp] * 5 + [vp]
+        L.sid_defor_elems_device.argtypes = [vp] * 5 + [C.c_int64] + [vp] * 3 + [vp]
+        L.sid_defor_debug_hypot.argtypes = [C.c_int, _f64p, _f64p, C.c_int64, _f64p]
+        L.sid_defor_last_error.restype = C.c_char_p
+        L.sid_defor_release.argtypes = [C.c_int]
     # SID_PM_LIB (A/B runs against the library of an earlier round) may lack the entry points added since
     optional = ('sid_pm_check', 'sid_pm_unpermute', 'sid_pm_rotate_and_match', 'sid_pm_get_template', 'sid_pm_get_hessian', 'sid_pm_estimate_run_time') if os.environ.get('SID_PM_LIB') else ()
     for name in SYMBOLS:
@@ -183,15 +197,15 @@ def _p(a, t):
 
 
 def release_workspaces(device=-1):
-    """Hand the cached device memory of the detector, the matcher and the first-guess evaluation back (``sid_orb_release``,
-    ``sid_ft_release``, ``sid_fg_release``; -1: every device).  No call on that device may be in flight.
+    """Hand the cached device memory of the detector, the matcher, the first-guess evaluation and the deformation back
+    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``; -1: every device).  No call on that device may be in flight.
     A process that never loaded the library has nothing cached: this returns without loading it (it is registered with
     atexit through pmlib.release_contexts, and loading means importing torch and initialising the GPU - not at interpreter
     shutdown, and not in a process that only used the host code)."""
     if _lib is None:
         return
     L = _lib
-    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release'):
+    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release'):
         if hasattr(L, name):
             getattr(L, name)(int(device))
 
@@ -650,4 +664,55 @@ def fg_distance_image(seeds, rows, cols, device=0):
     rc = L.sid_fg_distance_image(int(device), _p(seeds, _f64p), len(seeds), int(rows), int(cols), _p(out, _f64p))
     if rc != 0:
         raise SidPmError(rc, L.sid_fg_last_error().decode())
+    return out
+
+
+def _defor_check(rc):
+    if rc != 0:
+        msg = lib().sid_defor_last_error().decode()
+        if rc == DEFOR_ERR_INDEX:
+            raise IndexError(msg)
+        raise SidPmError(rc, msg)
+
+
+def defor_triangulation(x, y, u, v, t, device=0):
+    """``sid_defor_triangulation`` on host arrays: x, y, u, v float64 [n], t int32 / int64 [m, 3] (C-contiguous)
+    -> e1, e2, e3, a, p float64 [m].  An index outside [-n, n) raises IndexError."""
+    m = len(t)
+    out = [np.empty(m, dtype=np.float64) for _ in range(5)]
+    _defor_check(lib().sid_defor_triangulation(int(device), *[_p(a, _f64p) for a in (x, y, u, v)], len(x),
+                                               C.c_void_p(t.ctypes.data), int(t.dtype == np.int64), m,
+                                               *[_p(a, _f64p) for a in out]))
+    return tuple(out)
+
+
+def defor_elems(x, y, u, v, a, device=0):
+    """``sid_defor_elems`` on host arrays: x, y, u, v float64 [3, m], a float64 [m] (C-contiguous) -> e1, e2, e3 float64 [m]."""
+    m = len(a)
+    out = [np.empty(m, dtype=np.float64) for _ in range(3)]
+    _defor_check(lib().sid_defor_elems(int(device), *[_p(b, _f64p) for b in (x, y, u, v, a)], m, *[_p(b, _f64p) for b in out]))
+    return tuple(out)
+
+
+def defor_triangulation_device(x, y, u, v, n, t, t_int64, m, outs, stream):
+    """``sid_defor_triangulation_device`` on raw device pointers (torch ``data_ptr()``): outs = (e1, e2, e3, a, p)."""
+    _defor_check(lib().sid_defor_triangulation_device(*[C.c_void_p(int(q)) for q in (x, y, u, v)], int(n), C.c_void_p(int(t)),
+                                                      int(bool(t_int64)), int(m), *[C.c_void_p(int(q)) for q in outs],
+                                                      C.c_void_p(int(stream))))
+
+
+def defor_elems_device(x, y, u, v, a, m, outs, stream):
+    """``sid_defor_elems_device`` on raw device pointers: x, y, u, v [3, m], a [m]; outs = (e1, e2, e3)."""
+    _defor_check(lib().sid_defor_elems_device(*[C.c_void_p(int(q)) for q in (x, y, u, v, a)], int(m),
+                                              *[C.c_void_p(int(q)) for q in outs], C.c_void_p(int(stream))))
+
+
+def defor_debug_hypot(x, y, device=0):
+    """hypot(x, y) elementwise as the deformation kernel evaluates it (``sid_defor_debug_hypot``): on HIP device ``device``,
+    or with the same source compiled for the host (device=-1)."""
+    x, y = _f64(x).ravel(), _f64(y).ravel()
+    if x.size != y.size:
+        raise ValueError('x and y differ in size')
+    out = np.empty_like(x)
+    _defor_check(lib().sid_defor_debug_hypot(int(device), _p(x, _f64p), _p(y, _f64p), x.size, _p(out, _f64p)))
     return out
