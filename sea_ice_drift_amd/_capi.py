@@ -46,6 +46,9 @@ DEFOR_SYMBOLS = ('sid_defor_triangulation', 'sid_defor_elems', 'sid_defor_triang
                  'sid_defor_debug_hypot', 'sid_defor_last_error', 'sid_defor_release')
 DEFOR_ERR_INDEX = -32   # include/sid_defor.h SID_DEFOR_ERR_INDEX
 
+# every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
+PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
+
 _u8p = C.POINTER(C.c_uint8)
 _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
@@ -155,6 +158,13 @@ def lib():
         L.sid_defor_debug_hypot.argtypes = [C.c_int, _f64p, _f64p, C.c_int64, _f64p]
         L.sid_defor_last_error.restype = C.c_char_p
         L.sid_defor_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_prep_apply'):
+        vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
+        L.sid_prep_subsample.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, C.c_int64, vp, vp]
+        L.sid_prep_apply.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, _f64p] + plane + [vp]
+        L.sid_prep_spatial_mean.argtypes = [C.c_int64, C.c_int64, _f64p, vp, C.c_int64, vp]
+        L.sid_prep_debug_log10.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.sid_prep_last_error.restype = C.c_char_p
     # SID_PM_LIB (A/B runs against the library of an earlier round) may lack the entry points added since
     optional = ('sid_pm_check', 'sid_pm_unpermute', 'sid_pm_rotate_and_match', 'sid_pm_get_template', 'sid_pm_get_hessian', 'sid_pm_estimate_run_time') if os.environ.get('SID_PM_LIB') else ()
     for name in SYMBOLS:
@@ -716,3 +726,52 @@ def defor_debug_hypot(x, y, device=0):
     out = np.empty_like(x)
     _defor_check(lib().sid_defor_debug_hypot(int(device), _p(x, _f64p), _p(y, _f64p), x.size, _p(out, _f64p)))
     return out
+
+
+def _prep_check(rc):
+    if rc != 0:
+        raise SidPmError(rc, lib().sid_prep_last_error().decode())
+
+
+def _prep_coeffs(coeffs):
+    if coeffs is None:
+        return None, None
+    c = np.ascontiguousarray(coeffs, dtype=np.float64)
+    if c.shape != (6,):
+        raise ValueError('six float64 coefficients expected (col, col^2, row, row^2, col*row, 1), got shape %s' % (c.shape,))
+    return c, _p(c, _f64p)
+
+
+def prep_subsample(img, rows, cols, stride, ia, mask, dB, hh_factor, step, sub_ptr, stream=0):
+    """``sid_prep_subsample`` on raw device pointers: ``img`` a pointer, ``ia`` / ``mask`` (pointer, row stride) or None."""
+    ia_ptr, ia_stride = ia if ia is not None else (0, 0)
+    m_ptr, m_stride = mask if mask is not None else (0, 0)
+    _prep_check(lib().sid_prep_subsample(C.c_void_p(int(img)), rows, cols, stride, C.c_void_p(int(ia_ptr) or None), ia_stride,
+                                         C.c_void_p(int(m_ptr) or None), m_stride, int(bool(dB)), float(hh_factor), int(step),
+                                         C.c_void_p(int(sub_ptr)), C.c_void_p(int(stream))))
+
+
+def prep_apply(img, rows, cols, stride, ia, mask, dB, hh_factor, coeffs, out_ptr, out_stride, stream=0):
+    """``sid_prep_apply`` on raw device pointers; ``coeffs``: six float64 (host) or None for no detrend."""
+    ia_ptr, ia_stride = ia if ia is not None else (0, 0)
+    m_ptr, m_stride = mask if mask is not None else (0, 0)
+    keep, cp = _prep_coeffs(coeffs)
+    _prep_check(lib().sid_prep_apply(C.c_void_p(int(img)), rows, cols, stride, C.c_void_p(int(ia_ptr) or None), ia_stride,
+                                     C.c_void_p(int(m_ptr) or None), m_stride, int(bool(dB)), float(hh_factor), cp,
+                                     C.c_void_p(int(out_ptr)), out_stride, C.c_void_p(int(stream))))
+
+
+def prep_spatial_mean(rows, cols, coeffs, out_ptr, out_stride, stream=0):
+    """``sid_prep_spatial_mean``: the float64 polynomial image for six coefficients, into a device buffer."""
+    keep, cp = _prep_coeffs(coeffs)
+    if cp is None:
+        raise ValueError('six float64 coefficients expected')
+    _prep_check(lib().sid_prep_spatial_mean(rows, cols, cp, C.c_void_p(int(out_ptr)), out_stride, C.c_void_p(int(stream))))
+
+
+def prep_debug_log10(first_bits, n):
+    """``sid_prep_debug_log10``: (mismatches, library-route evaluations) of the dB step's float32 logarithm against
+    float(log10(double(x))) over the ``n`` float32 bit patterns from ``first_bits`` on."""
+    counts = (C.c_uint64 * 2)()
+    _prep_check(lib().sid_prep_debug_log10(int(first_bits), int(n), counts))
+    return int(counts[0]), int(counts[1])

@@ -2,8 +2,9 @@
 
 What ``pattern_matching`` touches: the two first-guess interpolators (reference lib.py:139-177 and
 :179-201), the grid scatter (lib.py:408-412) and a stand-in for ``nansat.NSR``; plus the uint8 staging step
-``get_uint8_image`` (lib.py:27-59), whose two full-image passes run on the GPU (include/sid_stage.h).
-Reading files (lib.py:256-340) and the geo/Haversine helpers are outside the hot path.
+``get_uint8_image`` (lib.py:27-59), whose two full-image passes run on the GPU (include/sid_stage.h), and the array steps of ``get_n`` in
+front of it (lib.py:318-331: dB, ``hh_angular_correction``, mask, ``get_spatial_mean``; include/sid_prep.h): ``prepare_image``.
+Reading files (lib.py:309-316, 333-340) and the geo/Haversine helpers are outside the hot path.
 """
 import numpy as np
 from scipy.interpolate import griddata
@@ -356,4 +357,193 @@ def get_uint8_image(image, vmin, vmax, pmin, pmax, device=0):
         vmin32 = ftype(vmin)
     out = torch.empty((rows, cols), dtype=torch.uint8, device=t.device)
     _capi.stage_scale_u8(t.data_ptr(), rows, cols, stride, vmin32, denom, out.data_ptr(), int(out.stride(0)), stream)
+    return out if is_tensor else out.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sigma0 preparation: the array half of get_n (reference lib.py:318-331) on the GPU (include/sid_prep.h)
+# ---------------------------------------------------------------------------------------------------------------------
+SPATIAL_MEAN_STEP = 50             # the reference's subsampling step of get_spatial_mean (lib.py:239)
+_PREP_WS = {}                      # per device: the subsample's device buffer and its pinned host copy
+
+
+def _prep_kind(image, what='image'):
+    """(is_tensor, rows, cols) of a 2-D float32 image: NumPy array or ROCm torch tensor with unit inner stride."""
+    import torch
+    if isinstance(image, torch.Tensor):
+        if image.dtype != torch.float32:
+            raise NotImplementedError('%s: float32 expected on the device (got %s)' % (what, image.dtype))
+        if image.dim() != 2:
+            raise ValueError('%s: 2-D array expected (got %d-D)' % (what, image.dim()))
+        if not image.is_cuda:
+            raise ValueError('a torch input must live on the GPU (pass NumPy arrays for host data)')
+        if image.stride(1) != 1 and image.shape[1] > 1:
+            raise NotImplementedError('%s: unit inner stride expected (row stride is free)' % what)
+        return True, int(image.shape[0]), int(image.shape[1])
+    a = np.asarray(image)
+    if a.dtype != np.float32:
+        raise NotImplementedError('%s: float32 expected on the device (got %s)' % (what, a.dtype))
+    if a.ndim != 2:
+        raise ValueError('%s: 2-D array expected (got %d-D)' % (what, a.ndim))
+    return False, int(a.shape[0]), int(a.shape[1])
+
+
+def _prep_side(arr, what, is_tensor, shape, mask=False):
+    """Check an optional plane (incidence angle: float32; mask: bool / uint8) against the image: same kind, same shape."""
+    import torch
+    if isinstance(arr, torch.Tensor) != is_tensor:
+        raise TypeError('%s: do not mix NumPy arrays and torch tensors in one call' % what)
+    if not is_tensor:
+        arr = np.asarray(arr)
+    if mask:
+        ok = arr.dtype in ((torch.bool, torch.uint8) if is_tensor else (np.dtype(bool), np.dtype(np.uint8)))
+        if not ok:
+            raise NotImplementedError('%s: bool or uint8 expected (got %s)' % (what, arr.dtype))
+    elif arr.dtype != (torch.float32 if is_tensor else np.float32):
+        raise NotImplementedError('%s: float32 expected on the device (got %s)' % (what, arr.dtype))
+    if tuple(arr.shape) != tuple(shape):
+        raise ValueError('%s: shape %s differs from the image\'s %s' % (what, tuple(arr.shape), tuple(shape)))
+    if is_tensor:
+        if not arr.is_cuda:
+            raise ValueError('a torch input must live on the GPU (pass NumPy arrays for host data)')
+        if arr.stride(1) != 1 and arr.shape[1] > 1:
+            raise NotImplementedError('%s: unit inner stride expected (row stride is free)' % what)
+    return arr
+
+
+def _prep_coeffs(coeffs):
+    c = np.ascontiguousarray(coeffs, dtype=np.float64)
+    if c.shape != (6,):
+        raise ValueError('spatial_mean_coeffs: six float64 coefficients expected (col, col^2, row, row^2, col*row, 1), '
+                         'got shape %s' % (c.shape,))
+    return c
+
+
+def _prep_upload(arr, dev, mask=False):
+    import torch
+    a = np.ascontiguousarray(arr)
+    if mask:
+        a = a.view(np.uint8)
+    return torch.from_numpy(a).to(dev)
+
+
+def _plane(t):
+    return (t.data_ptr(), int(t.stride(0)))
+
+
+def fit_spatial_mean(imgsub, step=SPATIAL_MEAN_STEP):
+    """The six coefficients of the reference's get_spatial_mean (lib.py:240-247) from ``imgsub`` = ``img[::step, ::step]``:
+    samples that are finite and above the subsample's 5th percentile, the int64 predictors [col, col^2, row, row^2,
+    col*row, 1] at the samples' pixel positions, ``np.linalg.lstsq(..., rcond=None)``.  NumPy's own calls on the host -
+    whatever they warn or raise for a degenerate subsample is what the caller gets."""
+    imgsub = np.asarray(imgsub)
+    colsub, rowsub = np.meshgrid(np.arange(0, imgsub.shape[1]) * step, np.arange(0, imgsub.shape[0]) * step)
+    gpi = np.isfinite(imgsub) * (imgsub > np.nanpercentile(imgsub, 5))
+    z, y, x = imgsub[gpi], rowsub[gpi], colsub[gpi]
+    predictors = np.array([x, x ** 2, y, y ** 2, x * y, np.ones_like(x)]).T
+    return np.linalg.lstsq(predictors, z, rcond=None)[0]
+
+
+def _prep_subsample(t, ia, mask, dB, factor, stream):
+    """``[::50, ::50]`` of the image after dB / HH correction / mask, as a NumPy array (a few ten thousand samples)."""
+    import torch
+    from . import _capi
+    rows, cols = int(t.shape[0]), int(t.shape[1])
+    nrs, ncs = -(-rows // SPATIAL_MEAN_STEP), -(-cols // SPATIAL_MEAN_STEP)
+    n = nrs * ncs
+    dev_index = t.device.index or 0
+    ws = _PREP_WS.get(dev_index)
+    if ws is None or ws[0].numel() < n:
+        cap = max(n, 65536)
+        ws = _PREP_WS[dev_index] = (torch.empty(cap, dtype=torch.float32, device=t.device),
+                                    torch.empty(cap, dtype=torch.float32, pin_memory=True))
+    d_sub, h_sub = ws
+    _capi.prep_subsample(t.data_ptr(), rows, cols, int(t.stride(0)), None if ia is None else _plane(ia),
+                         None if mask is None else _plane(mask), dB, factor, SPATIAL_MEAN_STEP, d_sub.data_ptr(), stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        h_sub[:n].copy_(d_sub[:n], non_blocking=True)
+    stream.synchronize()
+    return h_sub[:n].numpy().reshape(nrs, ncs).copy()
+
+
+def _prep_apply(image, incidence_angle, mask, dB, factor, remove_spatial_mean, coeffs, device):
+    """Checks, uploads and the one streaming pass: -> (float32 working image on the device, is_tensor)."""
+    import torch
+    from . import _capi
+    is_tensor, rows, cols = _prep_kind(image)
+    if incidence_angle is not None:
+        incidence_angle = _prep_side(incidence_angle, 'incidence_angle', is_tensor, (rows, cols))
+    if mask is not None:
+        mask = _prep_side(mask, 'mask', is_tensor, (rows, cols), mask=True)
+    if coeffs is not None:
+        coeffs = _prep_coeffs(coeffs)
+    if rows < 1 or cols < 1:
+        raise ValueError('image: empty array')
+    dev = image.device if is_tensor else torch.device('cuda', device)
+    t = image if is_tensor else _prep_upload(image, dev)
+    ia = None if incidence_angle is None else (incidence_angle if is_tensor else _prep_upload(incidence_angle, dev))
+    mk = None if mask is None else (mask if is_tensor else _prep_upload(mask, dev, mask=True))
+    stream = torch.cuda.current_stream(dev)
+    if remove_spatial_mean and coeffs is None:
+        coeffs = fit_spatial_mean(_prep_subsample(t, ia, mk, dB, factor, stream))
+    work = torch.empty((rows, cols), dtype=torch.float32, device=dev)
+    _capi.prep_apply(t.data_ptr(), rows, cols, int(t.stride(0)), None if ia is None else _plane(ia),
+                     None if mk is None else _plane(mk), dB, factor, coeffs if remove_spatial_mean else None,
+                     work.data_ptr(), int(work.stride(0)), stream.cuda_stream)
+    return work, is_tensor
+
+
+def hh_angular_correction(n, img, bandName, correct_hh_factor, device=0):
+    """sigma0_HH corrected for its incidence-angle dependence on the GPU: signature and result of the reference's
+    ``hh_angular_correction`` (lib.py:203-223): ``img - n['incidence_angle'] * correct_hh_factor`` in float32 when
+    ``bandName == 'sigma0_HH' and n.has_band('incidence_angle')``, otherwise ``img`` itself.  ``img`` and the incidence
+    angle: float32 NumPy arrays (uploaded; a NumPy array comes back) or ROCm torch tensors (a device tensor comes back);
+    ``correct_hh_factor`` a Python float (a weak scalar beside the float32 arrays, as in the reference)."""
+    if not (bandName == 'sigma0_HH' and n.has_band('incidence_angle')):
+        return img
+    out, is_tensor = _prep_apply(img, n['incidence_angle'], None, False, float(correct_hh_factor), False, None, device)
+    return out if is_tensor else out.cpu().numpy()
+
+
+def get_spatial_mean(img, device=0):
+    """Second-order polynomial approximation of the image's spatial mean brightness: signature and result of the
+    reference's ``get_spatial_mean`` (lib.py:225-254), a float64 image.  The fit to every 50th pixel in both directions
+    runs on the host (``fit_spatial_mean``); the device evaluates the polynomial at every pixel in the reference's order
+    of operations (include/sid_prep.h).  float32 NumPy array in, NumPy array out; ROCm torch tensor in, device tensor out."""
+    import torch
+    from . import _capi
+    is_tensor, rows, cols = _prep_kind(img, 'img')
+    if rows < 1 or cols < 1:
+        raise ValueError('img: empty array')
+    dev = img.device if is_tensor else torch.device('cuda', device)
+    stream = torch.cuda.current_stream(dev)
+    if is_tensor:
+        sub = _prep_subsample(img, None, None, False, 0.0, stream)
+    else:
+        sub = np.asarray(img)[::SPATIAL_MEAN_STEP, ::SPATIAL_MEAN_STEP]
+    coeffs = fit_spatial_mean(sub)
+    out = torch.empty((rows, cols), dtype=torch.float64, device=dev)
+    _capi.prep_spatial_mean(rows, cols, coeffs, out.data_ptr(), int(out.stride(0)), stream.cuda_stream)
+    return out if is_tensor else out.cpu().numpy()
+
+
+def prepare_image(image, dB=True, incidence_angle=None, correct_hh_factor=-0.27, mask=None, remove_spatial_mean=False,
+                  vmin=None, vmax=None, pmin=10, pmax=99, device=0, spatial_mean_coeffs=None):
+    """float32 sigma0 -> the uint8 image that feature tracking and pattern matching read: lines 318-331 of the reference's
+    ``get_n`` on arrays, keyword names and defaults from ``get_n`` (lib.py:256-268).
+
+    In ``get_n``'s order: ``dB`` (values <= 0 become NaN, then 10 * log10), the HH angular correction when
+    ``incidence_angle`` (float32, same shape) is given, ``mask`` (bool or uint8, same shape, True = invalid: those pixels
+    become NaN; stands in for ``get_invalid_mask``), ``remove_spatial_mean`` (minus the second-order polynomial fitted to
+    every 50th pixel; ``spatial_mean_coeffs`` - six float64 - skips the fit) and ``get_uint8_image(vmin, vmax, pmin, pmax)``.
+    The first four are one pass over the image on the device (include/sid_prep.h), the last is the staging step above.
+
+    NumPy arrays are uploaded and a NumPy array comes back; ROCm torch tensors (unit inner stride, any row stride) are read
+    in place on the current stream and a device tensor comes back.  The input is never modified.  Every step repeats
+    NumPy's float32 / float64 arithmetic operation for operation, with one documented exception: the float32 logarithm is
+    the float64 ``log10`` rounded once, which NumPy's own float32 ``log10`` misses by 1 ulp on about half of all inputs
+    (DESIGN.md section 16 has what that means for the uint8 image).  No CPU fallback."""
+    work, is_tensor = _prep_apply(image, incidence_angle, mask, bool(dB), float(correct_hh_factor), bool(remove_spatial_mean),
+                                  spatial_mean_coeffs, device)
+    out = get_uint8_image(work, vmin, vmax, pmin, pmax)
     return out if is_tensor else out.cpu().numpy()
