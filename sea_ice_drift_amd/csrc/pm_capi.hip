@@ -1611,11 +1611,13 @@ static int estimate_points(const double *border, int64_t n, int img_size, int n_
             }
             const sid::RpLdsLayout L4 = sid::rp_lds_layout(wn, wn, s, K <= sid::kRpGroup, rp_rows(rpp, 4), 0, sid::rp_tab_pitch(rpp), rp_own_hes(K, flags), sc.gs);
             const int per_cu = std::max(1, sc.cls), band = sc.band;            // (big layouts - class 0 - run one workgroup per CU, full table)
-            const int rows = sc.big ? 4 : rp_rows(rpp, band), nb = (r + rows - 1) / rows, tiles = 2 * L4.npair + L4.nsingle;
+            const int rows = sc.big ? 4 : rp_rows(rpp, band), tiles = 2 * L4.npair + L4.nsingle;
             const double per_row_tile = (double)((s + 1) / 2 + s / 2 + 1) / 2.0 + (double)(((s - 32 + 1) / 2) * 2);
             // work items are dealt to the wavefronts of the workgroup: the busiest wavefront sets the pace
             const int nwaves = per_cu == 1 ? 12 : 4;
-            const int units = ((nb * tiles + nwaves - 1) / nwaves) * nwaves, wunits = ((((r + 15) / 16) * tiles + nwaves - 1) / nwaves) * nwaves;
+            // (the sweep's items: rp_sweep_items - ragged single items where the full-table kernels pack the leftover columns of all bands)
+            const int sw_units = sid::rp_sweep_items(r, r, rows, sid::rp_sweep_ragged_ok(sc.big ? 0 : rpp)).units;
+            const int units = ((sw_units + nwaves - 1) / nwaves) * nwaves, wunits = ((((r + 15) / 16) * tiles + nwaves - 1) / nwaves) * nwaves;
             sweep = groups * (sc.big ? 1.0 : rpp == 2 ? 0.33 : rpp == 1 ? 0.55 : 1.0) * units * (rows * per_row_tile + 2.0);
             winner = wunits * 76.0;
             cls_factor = ((per_cu >= 4 && max_per_cu(rp, rpp) == 4) ? kFourPerCu : per_cu >= 3 ? 1.0 : per_cu == 2 ? kTwoPerCu : kOnePerCu) * (sc.gs ? F.gs : 1.0) * (sc.big ? kBigFactor : 1.0);

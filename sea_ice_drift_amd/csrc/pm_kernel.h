@@ -337,6 +337,90 @@ __host__ __device__ inline RpLdsLayout rp_lds_layout(int wh, int ww, int s, bool
     return L;
 }
 
+// ---- work items of the sweep (rp_sweep; the host's cost model counts them through the same functions) ----
+// A band of `rows` output rows is tiled into pair items of 32 placement columns (2 units of work) and single items of 16
+// (1 unit).  Today's tiling - the one RpLdsLayout::npair / nsingle describe, which the winner and the slot-group kernels
+// keep - tiles every band on its own: the rem = rw % 32 leftover columns of a band take one single item (rem <= 16) or a
+// whole further pair item, of which 16 - rem (32 - rem) columns do not exist.  The RAGGED tiling packs the leftover
+// columns of ALL bands into single items instead: lane n of ragged item i takes entry f = 16 i + n of the list "leftover
+// columns of the first band, of the second, ..." (bands in the sweep's middle-outwards order), i.e. its OWN band f / rem
+// and column 32 npair + f % rem - a single item addresses the window per lane anyway.  ceil(nbands rem / 16) single items
+// replace nbands single (or pair) items.  Chosen per shape by item units - a single item weighted by its measured cost where it
+// replaces pair items (rp_sweep_items) -; ties keep today's tiling.
+struct RpSweepItems {
+    int rows, nbands;           // output rows per item, bands
+    int npair;                  // pair items per band
+    int nsingle;                // today's tiling: single items per band (0 / 1); 0 when ragged
+    int rem;                    // ragged tiling: leftover columns per band (1 .. 31); 0 with today's tiling
+    int n_pair_items, n_single_items;   // of the whole point (single: one per band, or the ragged ones)
+    int units;                  // 2 n_pair_items + n_single_items
+};
+// ragged_ok (rp_sweep_ragged_ok): the full-table kernels without kept accumulators (slot groups map slots 8..15 to other
+// rows, and a kept accumulator table is padded to whole items of ONE band: they keep today's tiling)
+// (paired: 0 = full table, 1 / 2 = slot groups; -DSID_KEEP_ACC_FULL compiles kept accumulators into the full-table kernels too)
+#ifdef SID_KEEP_ACC_FULL
+__host__ __device__ constexpr bool rp_sweep_ragged_ok(int) { return false; }
+#else
+__host__ __device__ constexpr bool rp_sweep_ragged_ok(int paired) { return paired == 0; }
+#endif
+__host__ __device__ inline RpSweepItems rp_sweep_items(int rh, int rw, int rows, bool ragged_ok)
+{
+    RpSweepItems I;
+    I.rows = rows; I.nbands = (rh + rows - 1) / rows;
+    const int rem = rw % 32;
+    I.npair = rw / 32 + (rem > 16 ? 1 : 0);
+    I.nsingle = (rem > 0 && rem <= 16) ? 1 : 0;
+    I.rem = 0;
+    I.n_pair_items = I.nbands * I.npair; I.n_single_items = I.nbands * I.nsingle;
+    I.units = 2 * I.n_pair_items + I.n_single_items;
+    if (ragged_ok && rem != 0 && rem != 16) {
+        // rem < 16: fewer single items instead of one per band - fewer units, always taken.  rem > 16: single items instead
+        // of one more pair item per band; a single item takes MORE than half a pair item's time (five ds_read_b32 per step
+        // for one fragment instead of three ds_read_b64 for two, the scoring's per-item part, the lanes' bands apart in LDS) -
+        // measured per border, parent against ragged-by-units (profiles/r07_ab_ragged_tiles.txt): 4-row bands rem 18 -5.9 %,
+        // 22 +0.3 %, 24 +-0, 26 -0.7 %, 28 +3.3 %, 30 +5.3 % of the step; 8-row bands rem 22 -3.8 %, 26 -1.3 %.  So a single
+        // item counts kRpSingleCost / 32 of a pair item here: 24 with 4-row bands (ragged up to rem 20), 19 with 8-row bands
+        // (up to rem 26), and a tie keeps today's tiling.
+        const int nrag = (I.nbands * rem + 15) / 16, u = 2 * I.nbands * (rw / 32) + nrag;
+        const int single_cost = rows >= 8 ? 19 : 24;
+        const bool take = rem < 16 ? nrag < I.nbands : single_cost * nrag < 32 * I.nbands;
+        if (take && u < I.units) {
+            I.npair = rw / 32; I.nsingle = 0; I.rem = rem;
+            I.n_pair_items = I.nbands * I.npair; I.n_single_items = nrag; I.units = u;
+        }
+    }
+    return I;
+}
+// band of position `order` in the sweep's order: from the middle of the window outwards
+__host__ __device__ inline int rp_band_of_order(int order, int nbands)
+{
+    const int bc = (nbands - 1) >> 1;
+    return (order & 1) ? bc + ((order + 1) >> 1) : bc - (order >> 1);
+}
+// lane n (0 .. 15: the placement column of the MFMA tile) of single item `item`: its band, the first output row of that band,
+// its placement column, and whether it holds a placement at all.  A dead lane of a ragged item (past the end of the list)
+// points at the list's last placement: it reads valid bytes and is masked out of the scoring, as a column >= rw (x == rw ..
+// of today's single items: clamped by the caller where it addresses memory) is.
+struct RpSweepLane { int band, y0, x; bool live; };
+__host__ __device__ inline RpSweepLane rp_sweep_single_lane(const RpSweepItems &I, int rh, int rw, int item, int n)
+{
+    RpSweepLane P;
+    int order = item, c = n;
+    P.live = true;
+    if (I.rem) {
+        const int total = I.nbands * I.rem;
+        int f = 16 * item + n;
+        P.live = f < total;
+        if (!P.live) f = total - 1;
+        order = f / I.rem; c = f - order * I.rem;
+    }
+    P.band = rp_band_of_order(order, I.nbands);
+    P.y0 = rp_band_y0(P.band, I.nbands, rh, I.rows);
+    P.x = 32 * I.npair + c;
+    if (P.x >= rw) P.live = false;
+    return P;
+}
+
 // kept accumulators (PMArgs::gs_keep_acc): the table is padded to whole work items, so that the sweep stores without predicates -
 // cols_pad = the placement columns its tiles cover, rows_pad = bands x output rows per item.  (Measured, 3 angles: predicated
 // stores +6 % at border 30, stores of the lanes beyond the matrix redirected to one spare entry +2 %; the padding costs 30 %

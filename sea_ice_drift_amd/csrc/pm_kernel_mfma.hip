@@ -103,6 +103,7 @@ struct Geo {
     u32 patch_magic, rw_magic;       // same for ppitch/4 and for rw
     int band;                        // output rows per sweep work item (kernel template parameter)
     int wp_off, wp_pitch, wp_rows, strip_off, wrows, npair, nsingle;   // row-pair kernel (RpLdsLayout)
+    int sw_npair, sw_rem, sw_nsing;  // row-pair kernel, the SWEEP's work items (rp_sweep_items): pair items per band, leftover columns per band of the ragged tiling (0: today's), single items of the point
     int queue_cap;                   // row-pair kernel: entries of the candidate queue (RpLdsLayout::queue_cap)
     int hes_off, ccm_off;            // Hessian magnitudes and NCC matrix of the winning angle (f32 per placement)
     int si_off;                      // row-pair kernel: sum w' per placement kept from the sweep for the winner (0: none)

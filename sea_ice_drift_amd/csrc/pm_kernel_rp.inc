@@ -766,15 +766,20 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
     const bool force_b = m->any_const != 0;
 #define STAMP2(k) do { if (dbg_cycles && tid == 0) dbg_cycles[k] = (long long)clock64(); } while (0)
 
-    // Work items: nbands x npair pair items (32 placements, cost 2) and nbands x nsingle single items (16 placements,
-    // cost 1).  A wavefront takes every W-th pair item and then every W-th single item counted from the other end of
-    // the wavefronts, so that the ones that got one pair item fewer get one single item more (dealing items w, w + W,
-    // ... of the mixed list gave half the wavefronts only pair items and the others only single ones).
-    // Bands run from the middle of the window outwards: the peak is near the first guess, so the running maximum is
-    // high early and most items never reach the candidate pass.
-    const int nbands = (rh + ROWS - 1) / ROWS, bc = (nbands - 1) >> 1;
-    const int npair = G.npair, nsingle = G.nsingle, win_off = G.win_off, wp_off = G.wp_off, npos = G.npos;   // (LDS reads: once)
-    const int n_pair_items = nbands * npair, n_single_items = nbands * nsingle;
+    // Work items (rp_sweep_items): nbands x npair pair items (32 placements, cost 2), then the single items (16 placements,
+    // cost 1) - one per band for its leftover columns, or (full-table kernels, where that is fewer units) RAGGED ones that
+    // pack the leftover columns of all bands, every lane in a band of its own (rp_sweep_single_lane).  A wavefront takes
+    // every W-th pair item and then every W-th single item counted from the other end of the wavefronts, so that the ones
+    // that got one pair item fewer get one single item more (dealing items w, w + W, ... of the mixed list gave half the
+    // wavefronts only pair items and the others only single ones).
+    // Bands run from the middle of the window outwards (the leftover columns in the ragged items too): the peak is near the
+    // first guess, so the running maximum is high early and most items never reach the candidate pass.
+    constexpr bool RAG = rp_sweep_ragged_ok(PAIRED);
+    RpSweepItems I;
+    I.rows = ROWS; I.nbands = (rh + ROWS - 1) / ROWS; I.npair = RAG ? G.sw_npair : G.npair; I.rem = RAG ? G.sw_rem : 0;
+    const int nbands = I.nbands;
+    const int npair = I.npair, win_off = G.win_off, wp_off = G.wp_off, npos = G.npos;   // (LDS reads: once)
+    const int n_pair_items = nbands * npair, n_single_items = RAG ? G.sw_nsing : nbands * G.nsingle;
     const int my_pairs = wv < n_pair_items ? (n_pair_items - wv + kWavesM - 1) / kWavesM : 0;
     const int wr = kWavesM - 1 - wv;
     const int my_singles = wr < n_single_items ? (n_single_items - wr + kWavesM - 1) / kWavesM : 0;
@@ -785,36 +790,72 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
     int p_bo = wv / np1, p_xi = wv - p_bo * np1;
     for (int it = 0; it < my_pairs + my_singles; ++it) {
         const bool pair = it < my_pairs;                               // wavefront-uniform
-        int bo, xi;
-        if (pair) {
-            bo = p_bo; xi = p_xi;
-            p_bo += step_bo; p_xi += step_xi;
-            if (p_xi >= np1) { p_xi -= np1; ++p_bo; }
-        } else { bo = wr + (it - my_pairs) * kWavesM; xi = npair; }    // (at most one single item per band)
-        const int band = (bo & 1) ? bc + ((bo + 1) >> 1) : bc - (bo >> 1);
-        const int y0 = rp_band_y0(band, nbands, rh, ROWS), x0 = xi * 32;
         const int item = it == 0 ? wv : -1;                            // (phase-cycle stamps: first item of wavefront 0)
         const int ntile = pair ? 2 : 1;
-        if (item == wv) STAMP2(10);
-        const int xA = pair ? x0 + (n_l & 3) + 8 * (n_l >> 2) : x0 + n_l, xB = pair ? xA + 4 : rw;   // xB = rw: no tile B
+        if (RAG && item == wv) STAMP2(10);
+        // This lane's share of the item.  pA: row-major index of the placement of its accumulator row 0 in tile A (or the single
+        // tile); row t is t * rw further on, tile B four columns.  okbits, bit BAND k + t: accumulator row t of tile k lies
+        // inside the matrix.  In a pair item the rows are a mask of the band - wavefront-uniform without slot groups: scalar
+        // arithmetic - and the column one compare per tile; in a single item band and mask belong to the lane.
+        // wtlA / wtlB: the lane's byte of the transposed strip copy, mbo / msh: its window bytes of step 0 (rp_item_strip, rp_item_main).
+        // The slot-group kernels (and kept accumulators) have no ragged items: every item has ONE band, y0u, and the placement
+        // is kept as (y0u, xAu) - their lanes' rows differ by slot group (yup) and the accumulator table has a pitch of its own.
+        int pA = 0, y0u = 0, xAu = 0, xBu = 0, x0u = 0; u32 okbits, wtlA = 0, wtlB = 0, mbo = 0, msh = 0;
+        if (!RAG) {
+            int bo, xi;
+            if (pair) {
+                bo = p_bo; xi = p_xi;
+                p_bo += step_bo; p_xi += step_xi;
+                if (p_xi >= np1) { p_xi -= np1; ++p_bo; }
+            } else { bo = wr + (it - my_pairs) * kWavesM; xi = npair; }    // (one single item per band)
+            const int y0 = rp_band_y0(rp_band_of_order(bo, nbands), nbands, rh, ROWS), x0 = xi * 32;
+            if (item == wv) STAMP2(10);
+            const int xA = pair ? x0 + (n_l & 3) + 8 * (n_l >> 2) : x0 + n_l, xB = pair ? xA + 4 : rw;   // xB = rw: no tile B
+            const int rleft = rh - (y0 + yup);
+            const u32 rowmask = rleft >= BAND ? (1u << BAND) - 1u : rleft <= 0 ? 0u : (1u << rleft) - 1u;
+            okbits = (xA < rw ? rowmask : 0u) | (xB < rw ? rowmask << BAND : 0u);
+            y0u = y0; xAu = xA; xBu = xB; x0u = x0;
+        } else if (pair) {
+            const int bo = p_bo, xi = p_xi;
+            p_bo += step_bo; p_xi += step_xi;
+            if (p_xi >= np1) { p_xi -= np1; ++p_bo; }
+            const int y0 = rp_band_y0(rp_band_of_order(bo, nbands), nbands, rh, ROWS), x0 = xi * 32;
+            const int xA = x0 + (n_l & 3) + 8 * (n_l >> 2), xB = xA + 4;
+            const int rleft = rh - (y0 + yup);
+            const u32 rowmask = rleft >= BAND ? (1u << BAND) - 1u : rleft <= 0 ? 0u : (1u << rleft) - 1u;
+            okbits = (xA < rw ? rowmask : 0u) | (xB < rw ? rowmask << BAND : 0u);
+            pA = (y0 + yup) * rw + xA;
+            const int vA = xA < rw ? xA : rw - 1, vB = xB < rw ? xB : rw - 1;
+            wtlA = (u32)(wp_off + (vA + (q_l & 1)) * wp_pitch + y0 + 16 * (q_l >> 1));
+            wtlB = (u32)(wp_off + (vB + (q_l & 1)) * wp_pitch + y0 + 16 * (q_l >> 1));
+            mbo = (u32)(win_off + (y0 + (q_l >> 1)) * wpitch + x0 + 8 * (n_l >> 2) + 16 * (q_l & 1));
+            msh = (u32)(n_l & 3);
+        } else {
+            const RpSweepLane P = rp_sweep_single_lane(I, rh, rw, wr + (it - my_pairs) * kWavesM, n_l);
+            const int y0 = P.y0, xA = P.x;
+            const int rleft = rh - (y0 + yup);
+            const u32 rowmask = rleft >= BAND ? (1u << BAND) - 1u : rleft <= 0 ? 0u : (1u << rleft) - 1u;
+            okbits = P.live ? rowmask : 0u;
+            pA = (y0 + yup) * rw + xA;
+            const int vA = xA < rw ? xA : rw - 1;
+            wtlA = (u32)(wp_off + (vA + (q_l & 1)) * wp_pitch + y0 + 16 * (q_l >> 1));
+            const u32 sbyte = (u32)(xA + 16 * (q_l & 1));
+            mbo = (u32)(win_off + (y0 + (q_l >> 1)) * wpitch) + (sbyte & ~3u);
+            msh = sbyte & 3u;
+        }
         // operands of the scoring that do not depend on the MFMAs: issued now, landed long before they are needed.
         // The per-placement part of the scoring (dI, 1 / sqrt(dI)) is the same in the four lane quarters that hold the
         // slots of one placement column: every quarter computes it for its SHARE of the band's rows only (row_of(j))
         // and the quarters exchange the results (ds_bpermute), so sum w'^2 is fetched for the share alone.
-        // bit BAND k + t: accumulator row t of tile k lies inside the matrix.  The rows are a mask of the band (wavefront-uniform
-        // without slot groups: scalar arithmetic), the column one compare per tile.
+        auto pidx = [&](int k, int t) { return RAG ? pA + 4 * k + t * rw : (y0u + yup + t) * rw + (k == 0 ? xAu : xBu); };   // placement of accumulator row t, tile k
         u32 siis[2][NSH];
-        const int rleft = rh - (y0 + yup);
-        const u32 rowmask = rleft >= BAND ? (1u << BAND) - 1u : rleft <= 0 ? 0u : (1u << rleft) - 1u;
-        const u32 okbits = (xA < rw ? rowmask : 0u) | (xB < rw ? rowmask << BAND : 0u);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int x = k == 0 ? xA : xB;
 #pragma unroll
             for (int j = 0; j < NSH; ++j) {
                 const int t = row_of(j);
-                const bool ok = (x < rw) & (y0 + yup + t < rh);
-                siis[k][j] = sii_at(sii, ok ? (y0 + yup + t) * rw + x : 0);
+                const bool ok = RAG ? ((okbits >> (BAND * k + t)) & 1u) != 0u : ((k == 0 ? xAu : xBu) < rw) & (y0u + yup + t < rh);
+                siis[k][j] = sii_at(sii, ok ? pidx(k, t) : 0);
             }
         }
         const u32 gkey = m->gmax_key;
@@ -822,28 +863,34 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
 #pragma unroll
         for (int t = 0; t < BAND; ++t) { accA[t] = v4i{0, 0, 0, 0}; accB[t] = v4i{0, 0, 0, 0}; }
         // strip columns first (their LDS latency overlaps the first reads of the main loop), then the 32 main columns
-        {
-            const int vA = xA < rw ? xA : rw - 1;
-            rp_item_strip<S, BAND>(accA, (u32)(wp_off + (vA + (q_l & 1)) * wp_pitch + y0 + 16 * (q_l >> 1)), wp_pitch, 16 * (q_l >> 1), fl);
+        if (!RAG) {
+            const int vA = xAu < rw ? xAu : rw - 1;
+            rp_item_strip<S, BAND>(accA, (u32)(wp_off + (vA + (q_l & 1)) * wp_pitch + y0u + 16 * (q_l >> 1)), wp_pitch, 16 * (q_l >> 1), fl);
             if (pair) {
-                const int vB = xB < rw ? xB : rw - 1;
-                rp_item_strip<S, BAND>(accB, (u32)(wp_off + (vB + (q_l & 1)) * wp_pitch + y0 + 16 * (q_l >> 1)), wp_pitch, 16 * (q_l >> 1), fl);
+                const int vB = xBu < rw ? xBu : rw - 1;
+                rp_item_strip<S, BAND>(accB, (u32)(wp_off + (vB + (q_l & 1)) * wp_pitch + y0u + 16 * (q_l >> 1)), wp_pitch, 16 * (q_l >> 1), fl);
             }
+        } else {
+            rp_item_strip<S, BAND>(accA, wtlA, wp_pitch, 16 * (q_l >> 1), fl);
+            if (pair) rp_item_strip<S, BAND>(accB, wtlB, wp_pitch, 16 * (q_l >> 1), fl);
         }
         if (pair) {
             v4i acc[BAND][2];
 #pragma unroll
             for (int t = 0; t < BAND; ++t) { acc[t][0] = accA[t]; acc[t][1] = accB[t]; }
-            rp_item_main<S, true, BAND, PAIRED, PITCH>(acc, la, (u32)(win_off + (y0 + (q_l >> 1)) * wpitch + x0 + 8 * (n_l >> 2) + 16 * (q_l & 1)),
-                                  2 * wpitch, (u32)(n_l & 3), a_grp);
+            if (!RAG) { mbo = (u32)(win_off + (y0u + (q_l >> 1)) * wpitch + x0u + 8 * (n_l >> 2) + 16 * (q_l & 1)); msh = (u32)(n_l & 3); }
+            rp_item_main<S, true, BAND, PAIRED, PITCH>(acc, la, mbo, 2 * wpitch, msh, a_grp);
 #pragma unroll
             for (int t = 0; t < BAND; ++t) { accA[t] = acc[t][0]; accB[t] = acc[t][1]; }
         } else {
             v4i acc[BAND][1];
 #pragma unroll
             for (int t = 0; t < BAND; ++t) acc[t][0] = accA[t];
-            const u32 sbyte = (u32)(x0 + n_l + 16 * (q_l & 1));
-            rp_item_main<S, false, BAND, PAIRED, PITCH>(acc, la, (u32)(win_off + (y0 + (q_l >> 1)) * wpitch) + (sbyte & ~3u), 2 * wpitch, sbyte & 3u, a_grp);
+            if (!RAG) {
+                const u32 sbyte = (u32)(x0u + n_l + 16 * (q_l & 1));
+                mbo = (u32)(win_off + (y0u + (q_l >> 1)) * wpitch) + (sbyte & ~3u); msh = sbyte & 3u;
+            }
+            rp_item_main<S, false, BAND, PAIRED, PITCH>(acc, la, mbo, 2 * wpitch, msh, a_grp);
 #pragma unroll
             for (int t = 0; t < BAND; ++t) accA[t] = acc[t][0];
         }
@@ -852,7 +899,7 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
             // (the table is padded to whole items: no predicates)
             unsigned char *ab = reinterpret_cast<unsigned char *>(const_cast<u32 *>(sii) + gsa) + 16u * (u32)(q_l & (SPG / 4 - 1));
             const u32 pitchb = (u32)gsa_rw * (4u * SPG);
-            u32 o = (u32)((y0 + yup) * gsa_rw + xA) * (4u * SPG);
+            u32 o = (u32)((y0u + yup) * gsa_rw + xAu) * (4u * SPG);
 #pragma unroll
             for (int t = 0; t < BAND; ++t) {
                 *reinterpret_cast<v4i *>(ab + o) = accA[t];
@@ -912,7 +959,7 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
                     }
                     // (where the residency class has room: sum w' of the placement kept for the winner's matrix, rp_lds_layout)
                     if (keep_si && ((okbits >> (BAND * k + tj)) & 1u))
-                        sii_put(reinterpret_cast<u32 *>(si_tab), (y0 + yup + tj) * rw + (k == 0 ? xA : xB), (u32)sw);
+                        sii_put(reinterpret_cast<u32 *>(si_tab), pidx(k, tj), (u32)sw);
 #ifdef SID_ABL_NO_RI
                     float ri = __int_as_float(0x3a000000 + (sw & 0xff) + (int)(siis[k][j] & 0xff));
 #else
@@ -975,21 +1022,20 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
             for (int k = 0; k < 2; ++k) {
                 if (k < ntile) {
                     const v4i (&acc)[BAND] = k == 0 ? accA : accB;
-                    const int x = k == 0 ? xA : xB;
 #pragma unroll
                     for (int t = 0; t < BAND; ++t) {
                         const bool ok = (okbits >> (BAND * k + t)) & 1u;
                         const bool rowhit = ok && (force_b || !(rowv[k][t] < thr));  // true for NaN
                         if (__ballot(rowhit) == 0ull) continue;       // wavefront-uniform
                         const float swf = (float)swp[k][t];
-                        const u32 siiv_kt = sii_at(sii, ok ? (y0 + yup + t) * rw + x : 0);
+                        const u32 siiv_kt = sii_at(sii, ok ? pidx(k, t) : 0);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int ai = __mul24(nmT[r], swp[k][t]) + acc[t][r];
                             const float v = fmaf(swf, cT[r], (float)ai);
                             const float e = fmaf(v, aT[r], bias[r]) * rIf[k][t];
                             if (ok && bias[r] == 0.0f && !(e < thr)) {                 // live slot; true for NaN
-                                const int key = (a0 + ((4 * q_l + r) & (SPG - 1))) * npos + (y0 + yup + t) * rw + x;
+                                const int key = (a0 + ((4 * q_l + r) & (SPG - 1))) * npos + pidx(k, t);
                                 const u32 slot = atomicAdd(&m->qcount, 1u);
                                 if (slot < (u32)G.queue_cap) queue[slot] = make_uint4((u32)acc[t][r], (u32)swp[k][t], siiv_kt, (u32)key);
                                 else ovf |= 1ull << (4 * BAND * k + 4 * t + r);
@@ -1005,7 +1051,7 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
                     if (!((ovf >> b) & 1ull)) continue;
                     const int k = b / (4 * BAND), t = (b >> 2) & (BAND - 1), r = b & 3;
                     int pv = 0, sw = 0;
-                    const u32 si = sii_at(sii, (y0 + yup + t) * rw + (k == 0 ? xA : xB));   // (flagged values are valid placements)
+                    const u32 si = sii_at(sii, pidx(k, t));   // (flagged values are valid placements)
 #pragma unroll
                     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -1016,7 +1062,7 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
                             for (int rr = 0; rr < 4; ++rr) pv = (hit & (r == rr)) ? (kk == 0 ? accA[tt][rr] : accB[tt][rr]) : pv;
                         }
                     const int a = (4 * q_l + r) & (SPG - 1);
-                    const int key = (a0 + a) * npos + (y0 + yup + t) * rw + (k == 0 ? xA : xB);
+                    const int key = (a0 + a) * npos + pidx(k, t);
                     take_better(sc, exact_from_sums(pv, sw, si, nd, m->sTd[a0 + a], m->rTd[a0 + a], m->constT[a0 + a] != 0), key);
                 }
             }
@@ -1691,6 +1737,10 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
         G->trow_bytes = L.trow_bytes; G->queue_cap = L.queue_cap;
         G->wp_off = L.wp_off; G->wp_pitch = L.wp_pitch; G->wp_rows = L.wp_rows; G->strip_off = L.strip_off;
         G->wrows = L.wrows; G->npair = L.npair; G->nsingle = L.nsingle;
+        if (rp_sweep_ragged_ok(PAIRED)) {                              // (the other kernels sweep the tiling above)
+            const RpSweepItems I = rp_sweep_items(rh, rw, BAND, true);
+            G->sw_npair = I.npair; G->sw_rem = I.rem; G->sw_nsing = I.n_single_items;
+        }
         // 5 KB for the Hessian's histogram and key list behind the NCC matrix of the winning angle, when the winner is
         // staged from the operand table (one group of angles) and the fused Hessian may run (no hes_smth / mcc_norm)
         const int hist_off = BIG ? L.u_off + 2 * L.trow_bytes : L.ccm_off + round_up(rh * rw * 4, 16);
