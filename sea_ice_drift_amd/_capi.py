@@ -49,6 +49,9 @@ DEFOR_ERR_INDEX = -32   # include/sid_defor.h SID_DEFOR_ERR_INDEX
 # every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
 PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
 
+# every symbol include/sid_mask.h declares (the invalid-pixel mask: zoomed water mask OR non-finite pixels; same library)
+MASK_SYMBOLS = ('sid_mask_workspace_bytes', 'sid_mask_landmask', 'sid_mask_invalid', 'sid_mask_last_error')
+
 _u8p = C.POINTER(C.c_uint8)
 _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
@@ -165,6 +168,14 @@ def lib():
         L.sid_prep_spatial_mean.argtypes = [C.c_int64, C.c_int64, _f64p, vp, C.c_int64, vp]
         L.sid_prep_debug_log10.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
         L.sid_prep_last_error.restype = C.c_char_p
+    if hasattr(L, 'sid_mask_invalid'):
+        vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
+        raster = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]          # d_wm, h, w, wm_stride, H, W, d_work
+        L.sid_mask_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+        L.sid_mask_workspace_bytes.restype = C.c_int64
+        L.sid_mask_landmask.argtypes = raster + plane + plane + [vp]
+        L.sid_mask_invalid.argtypes = raster + plane + [C.c_int] + plane + [C.c_float] + plane + plane + [vp]
+        L.sid_mask_last_error.restype = C.c_char_p
     # SID_PM_LIB (A/B runs against the library of an earlier round) may lack the entry points added since
     optional = ('sid_pm_check', 'sid_pm_unpermute', 'sid_pm_rotate_and_match', 'sid_pm_get_template', 'sid_pm_get_hessian', 'sid_pm_estimate_run_time') if os.environ.get('SID_PM_LIB') else ()
     for name in SYMBOLS:
@@ -775,3 +786,36 @@ def prep_debug_log10(first_bits, n):
     counts = (C.c_uint64 * 2)()
     _prep_check(lib().sid_prep_debug_log10(int(first_bits), int(n), counts))
     return int(counts[0]), int(counts[1])
+
+
+def _mask_check(rc):
+    if rc != 0:
+        raise SidPmError(rc, lib().sid_mask_last_error().decode())
+
+
+def mask_workspace_bytes(h, w):
+    """``sid_mask_workspace_bytes``: device scratch for a water mask of ``h`` x ``w``."""
+    return int(lib().sid_mask_workspace_bytes(int(h), int(w)))
+
+
+def _vp(ptr):
+    return C.c_void_p(int(ptr) or None)
+
+
+def mask_landmask(wm, h, w, H, W, work_ptr, mask, wmz, stream=0):
+    """``sid_mask_landmask`` on raw device pointers: ``wm`` / ``mask`` / ``wmz`` are (pointer, row stride), the last two or None."""
+    m_ptr, m_stride = mask if mask is not None else (0, 0)
+    z_ptr, z_stride = wmz if wmz is not None else (0, 0)
+    _mask_check(lib().sid_mask_landmask(_vp(wm[0]), int(h), int(w), int(wm[1]), int(H), int(W), _vp(work_ptr), _vp(m_ptr), m_stride,
+                                        _vp(z_ptr), z_stride, C.c_void_p(int(stream))))
+
+
+def mask_invalid(wm, h, w, H, W, work_ptr, img, dB, ia, hh_factor, mask, wmz=None, stream=0):
+    """``sid_mask_invalid`` on raw device pointers: ``img`` / ``mask`` are (pointer, row stride); ``wm`` (with ``h``, ``w``, ``work_ptr``),
+    ``ia`` and ``wmz`` are (pointer, row stride) or None."""
+    w_ptr, w_stride = wm if wm is not None else (0, 0)
+    ia_ptr, ia_stride = ia if ia is not None else (0, 0)
+    z_ptr, z_stride = wmz if wmz is not None else (0, 0)
+    _mask_check(lib().sid_mask_invalid(_vp(w_ptr), int(h), int(w), int(w_stride), int(H), int(W), _vp(work_ptr), _vp(img[0]), int(img[1]),
+                                       int(bool(dB)), _vp(ia_ptr), int(ia_stride), float(hh_factor), _vp(mask[0]), int(mask[1]),
+                                       _vp(z_ptr), int(z_stride), C.c_void_p(int(stream))))

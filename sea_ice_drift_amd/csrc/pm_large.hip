@@ -131,60 +131,7 @@ __device__ __forceinline__ int lw_sample(const uint8_t *img, long long stride, l
 // ---- rot_order 2..5 (pmlib.py:112-113: scipy's affine_transform with order = n): spline weights and taps over the prefiltered
 // image (oracle: sid_oracle_get_template_spline; weights and coefficients pinned against scipy itself, fixture G1c against the
 // reference's get_template) ----
-__device__ __forceinline__ void lw_spline_weights(double x, int order, double *w)
-{
-    x -= floor((order & 1) ? x : x + 0.5);
-    double y = x, z = 1.0 - x, t;
-    switch (order) {
-    case 2:
-        w[1] = 0.75 - x * x;
-        y = 0.5 - x;
-        w[0] = 0.5 * y * y;
-        break;
-    case 3:
-        w[1] = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0;
-        w[2] = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0;
-        w[0] = z * z * z / 6.0;
-        break;
-    case 4:
-        t = x * x;
-        w[2] = t * (t * 0.25 - 0.625) + 115.0 / 192.0;
-        y = 1.0 + x;
-        w[1] = y * (y * (y * (5.0 - y) / 6.0 - 1.25) + 5.0 / 24.0) + 55.0 / 96.0;
-        z = 1.0 - x;
-        w[3] = z * (z * (z * (5.0 - z) / 6.0 - 1.25) + 5.0 / 24.0) + 55.0 / 96.0;
-        y = 0.5 - x;
-        t = y * y;
-        w[0] = t * t / 24.0;
-        break;
-    default:
-        t = y * y;
-        w[2] = t * (t * (0.25 - y / 12.0) - 0.5) + 0.55;
-        t = z * z;
-        w[3] = t * (t * (0.25 - z / 12.0) - 0.5) + 0.55;
-        y = x + 1.0;
-        w[1] = y * (y * (y * (y * (y / 24.0 - 0.375) + 1.25) - 1.75) + 0.625) + 0.425;
-        y = 2.0 - x;
-        w[4] = y * (y * (y * (y * (y / 24.0 - 0.375) + 1.25) - 1.75) + 0.625) + 0.425;
-        z = 1.0 - x;
-        t = z * z;
-        w[0] = z * t * t / 120.0;
-        break;
-    }
-    double last = 1.0;
-    for (int i = 0; i < order; ++i) last -= w[i];
-    w[order] = last;
-}
-
-__device__ __forceinline__ long long lw_spline_mirror(long long idx, long long len)
-{
-    if (len <= 1) return 0;
-    const long long s2 = 2 * len - 2;
-    if (idx < 0) { idx = s2 * (-idx / s2) + idx; return idx <= 1 - len ? idx + s2 : -idx; }
-    if (idx >= len) { idx -= s2 * (idx / s2); if (idx >= len) idx = s2 - idx; }
-    return idx;
-}
-
+// (lw_spline_weights and lw_spline_mirror: pm_large.h, shared with landmask.hip)
 __device__ __forceinline__ int lw_sample_spline(const double *coef, long long rows, long long cols, double c, double r, const double *rot4,
                                                 int i, int j, int order)
 {

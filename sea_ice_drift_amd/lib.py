@@ -527,6 +527,138 @@ def get_spatial_mean(img, device=0):
     return out if is_tensor else out.cpu().numpy()
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# invalid-pixel mask: get_invalid_mask (reference lib.py:342-373) on the GPU (include/sid_mask.h)
+# ---------------------------------------------------------------------------------------------------------------------
+_MASK_WS = {}                      # per device: the scratch of the water-mask prefilter (grow-only)
+
+
+def _mask_raster(wm, is_tensor):
+    """Check a water-mask raster (2-D uint8, the image's kind, both axes longer than 1) -> (the raster, h, w)."""
+    import torch
+    if isinstance(wm, torch.Tensor) != is_tensor:
+        raise TypeError('watermask: do not mix NumPy arrays and torch tensors in one call')
+    if not is_tensor:
+        wm = np.asarray(wm)
+    if wm.dtype != (torch.uint8 if is_tensor else np.uint8):
+        raise NotImplementedError('watermask: uint8 expected (got %s).  The MODIS water mask nansat serves is a byte raster; a raster of '
+                                  'another dtype - float64 zeros, say, whose unrounded spline is compared with 2 - follows another '
+                                  'specification and is out of scope' % (wm.dtype,))
+    if len(wm.shape) != 2:
+        raise ValueError('watermask: 2-D array expected (got %d-D)' % len(wm.shape))
+    h, w = int(wm.shape[0]), int(wm.shape[1])
+    if h < 1 or w < 1:
+        raise ValueError('watermask: empty array')
+    if h < 2 or w < 2:
+        raise ValueError('watermask: shape %s has an axis of length 1 (SciPy does not prefilter such an axis; not supported)' % ((h, w),))
+    if is_tensor:
+        if not wm.is_cuda:
+            raise ValueError('a torch input must live on the GPU (pass NumPy arrays for host data)')
+        if wm.stride(1) != 1:
+            raise NotImplementedError('watermask: unit inner stride expected (row stride is free)')
+    return wm, h, w
+
+
+def _zoom_shape_check(h, w, H, W):
+    """The shape scipy.ndimage.zoom gives the reference's call - round(n_in * (n_out / n_in)) per axis - must be the image's:
+    where it is not, the reference's ``mask[wmz == 2]`` raises IndexError, and so does this."""
+    got = tuple(int(round(n_in * (n_out / n_in))) for n_in, n_out in ((h, H), (w, W)))
+    if got != (H, W):
+        raise IndexError('boolean index did not match: the water mask of %s zooms to %s, the image is %s' % ((h, w), got, (H, W)))
+
+
+def _mask_workspace(dev, h, w):
+    import torch
+    from . import _capi
+    need = _capi.mask_workspace_bytes(h, w)
+    key = dev.index or 0
+    ws = _MASK_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _MASK_WS[key] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _invalid_plane(t, ia, dB, factor, wm, wmz=None):
+    """uint8 device plane, 1 = invalid: land (``wm``: device uint8 raster or None) OR the pixel of the device image ``t`` is not
+    finite after dB / HH (``t`` None: land alone, of the shape of ``wmz``, which then receives the zoomed bytes)."""
+    import torch
+    from . import _capi
+    ref = t if t is not None else wmz
+    H, W, dev = int(ref.shape[0]), int(ref.shape[1]), ref.device
+    stream = torch.cuda.current_stream(dev)
+    h = w = 0
+    work = None
+    if wm is not None:
+        h, w = int(wm.shape[0]), int(wm.shape[1])
+        work = _mask_workspace(dev, h, w)
+    with torch.cuda.device(dev):
+        if t is None:
+            _capi.mask_landmask(_plane(wm), h, w, H, W, work.data_ptr(), None, _plane(wmz), stream.cuda_stream)
+            return wmz
+        plane = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        _capi.mask_invalid(None if wm is None else _plane(wm), h, w, H, W, 0 if work is None else work.data_ptr(), _plane(t), dB,
+                           None if ia is None else _plane(ia), factor, _plane(plane), None, stream.cuda_stream)
+    return plane
+
+
+def zoom_landmask(wm, shape, device=0):
+    """The uint8 image ``scipy.ndimage.zoom(maximum_filter(np.minimum(wm, 2), 3), np.array(shape) / np.array(wm.shape))`` returns
+    (lines 367-369 of the reference's ``get_invalid_mask``; SciPy's defaults: cubic spline, mode 'constant', prefilter), every byte
+    of it, computed on the GPU (include/sid_mask.h).  ``wm``: 2-D uint8 NumPy array (a NumPy array comes
+    back) or ROCm torch tensor (a device tensor comes back); never modified.  No CPU fallback."""
+    import torch
+    is_tensor = isinstance(wm, torch.Tensor)
+    wm, h, w = _mask_raster(wm, is_tensor)
+    H, W = (int(v) for v in shape)
+    if H < 1 or W < 1:
+        raise ValueError('shape: empty array')
+    _zoom_shape_check(h, w, H, W)
+    dev = wm.device if is_tensor else torch.device('cuda', device)
+    t = wm if is_tensor else _prep_upload(wm, dev)
+    out = _invalid_plane(None, None, False, 0.0, t, wmz=torch.empty((H, W), dtype=torch.uint8, device=dev))
+    return out if is_tensor else out.cpu().numpy()
+
+
+def invalid_mask(img, watermask=None, device=0):
+    """bool mask of the pixels that are NaN, +-inf or land: what the reference's ``get_invalid_mask`` (lib.py:342-373) computes
+    from the image and the water-mask raster ``n.watermask()[1]`` - land is where ``zoom_landmask(watermask, img.shape) == 2``.
+    ``watermask=None``: ``isnan(img) | isinf(img)`` alone.  ``img``: 2-D float32, ``watermask``: 2-D uint8; both NumPy arrays (a
+    NumPy array comes back) or both ROCm torch tensors (a device tensor comes back); neither is modified.  No CPU fallback."""
+    import torch
+    is_tensor, H, W = _prep_kind(img, 'img')
+    if H < 1 or W < 1:
+        raise ValueError('img: empty array')
+    if watermask is not None:
+        watermask, h, w = _mask_raster(watermask, is_tensor)
+        _zoom_shape_check(h, w, H, W)
+    dev = img.device if is_tensor else torch.device('cuda', device)
+    t = img if is_tensor else _prep_upload(img, dev)
+    wm = None if watermask is None else (watermask if is_tensor else _prep_upload(watermask, dev))
+    out = _invalid_plane(t, None, False, 0.0, wm).view(torch.bool)
+    return out if is_tensor else out.cpu().numpy()
+
+
+def get_invalid_mask(img, n, landmask_border, device=0):
+    """Mask of invalid pixels (land, coast, NaN, inf) on the GPU: signature, protocol and result of the reference's
+    ``get_invalid_mask`` (lib.py:342-373): ``n.resize(1. / landmask_border)``, ``n.watermask()[1]`` - when that raises, 'Cannot add
+    landmask' is printed and the mask has no land - ``n.undo()``, then ``invalid_mask(img, wm)``.  ``img``: float32 NumPy array
+    or ROCm torch tensor (the raster nansat returns is then uploaded); the raster is not modified."""
+    import torch
+    is_tensor, _, _ = _prep_kind(img, 'img')
+    n.resize(1. / landmask_border)
+    try:
+        wm = n.watermask()[1]
+    except:                                      # noqa: E722 - the reference's bare except (lib.py:364)
+        print('Cannot add landmask')
+        wm = None
+    n.undo()
+    if is_tensor and wm is not None and not isinstance(wm, torch.Tensor):
+        wm = np.asarray(wm)
+        if wm.dtype == np.uint8 and wm.ndim == 2 and wm.size:
+            wm = _prep_upload(wm, img.device)
+    return invalid_mask(img, wm, device)
+
+
 def prepare_image(image, dB=True, incidence_angle=None, correct_hh_factor=-0.27, mask=None, remove_spatial_mean=False,
                   vmin=None, vmax=None, pmin=10, pmax=99, device=0, spatial_mean_coeffs=None):
     """float32 sigma0 -> the uint8 image that feature tracking and pattern matching read: lines 318-331 of the reference's
@@ -542,8 +674,50 @@ def prepare_image(image, dB=True, incidence_angle=None, correct_hh_factor=-0.27,
     in place on the current stream and a device tensor comes back.  The input is never modified.  Every step repeats
     NumPy's float32 / float64 arithmetic operation for operation, with one documented exception: the float32 logarithm is
     the float64 ``log10`` rounded once, which NumPy's own float32 ``log10`` misses by 1 ulp on about half of all inputs
-    (DESIGN.md section 16 has what that means for the uint8 image).  No CPU fallback."""
+    (DESIGN.md section 16 has what that means for the uint8 image).  No CPU fallback.
+
+    ``prepare_image_masked`` below is this function with ``get_n``'s ``mask_invalid`` step computed on the device as well."""
     work, is_tensor = _prep_apply(image, incidence_angle, mask, bool(dB), float(correct_hh_factor), bool(remove_spatial_mean),
                                   spatial_mean_coeffs, device)
+    out = get_uint8_image(work, vmin, vmax, pmin, pmax)
+    return out if is_tensor else out.cpu().numpy()
+
+
+def prepare_image_masked(image, dB=True, incidence_angle=None, correct_hh_factor=-0.27, mask=None, remove_spatial_mean=False,
+                         vmin=None, vmax=None, pmin=10, pmax=99, device=0, spatial_mean_coeffs=None, mask_invalid=False,
+                         watermask=None):
+    """``prepare_image`` with two more keywords at the end, whose defaults make it ``prepare_image`` itself (that function keeps
+    the signature its callers know): ``mask_invalid=True`` is ``get_n``'s own ``mask_invalid`` - the device computes
+    ``get_invalid_mask`` of the image after dB / HH (NaN, +-inf and - with ``watermask``, the uint8 raster ``n.watermask()[1]``
+    at 1 / landmask_border of the resolution, of the image's kind - land: ``invalid_mask``), ORs ``mask`` in when one is given,
+    and that plane is the mask of ``prepare_image``'s steps; it never leaves the device.  So +-inf become NaN before the
+    percentiles, as in ``get_n``.  ``watermask`` without ``mask_invalid=True`` raises ValueError."""
+    if watermask is not None and not mask_invalid:
+        raise ValueError('watermask: needs mask_invalid=True')
+    if not mask_invalid:
+        return prepare_image(image, dB, incidence_angle, correct_hh_factor, mask, remove_spatial_mean, vmin, vmax, pmin, pmax, device,
+                             spatial_mean_coeffs)
+    import torch
+    is_tensor, rows, cols = _prep_kind(image)
+    if incidence_angle is not None:
+        incidence_angle = _prep_side(incidence_angle, 'incidence_angle', is_tensor, (rows, cols))
+    if mask is not None:
+        mask = _prep_side(mask, 'mask', is_tensor, (rows, cols), mask=True)
+    if spatial_mean_coeffs is not None:
+        spatial_mean_coeffs = _prep_coeffs(spatial_mean_coeffs)
+    if rows < 1 or cols < 1:
+        raise ValueError('image: empty array')
+    if watermask is not None:
+        watermask, h, w = _mask_raster(watermask, is_tensor)
+        _zoom_shape_check(h, w, rows, cols)
+    dev = image.device if is_tensor else torch.device('cuda', device)
+    up = (lambda a, **k: a) if is_tensor else (lambda a, **k: _prep_upload(a, dev, **k))
+    image = up(image)
+    incidence_angle = None if incidence_angle is None else up(incidence_angle)
+    plane = _invalid_plane(image, incidence_angle, bool(dB), float(correct_hh_factor), None if watermask is None else up(watermask))
+    if mask is not None:
+        plane |= (up(mask, mask=True) != 0).view(torch.uint8)
+    work, _ = _prep_apply(image, incidence_angle, plane, bool(dB), float(correct_hh_factor), bool(remove_spatial_mean),
+                          spatial_mean_coeffs, device)
     out = get_uint8_image(work, vmin, vmax, pmin, pmax)
     return out if is_tensor else out.cpu().numpy()
