@@ -119,22 +119,26 @@ def match(kp1, descr1, kp2, descr2, ratio_test=0.7, device=0, verbose=False):
 
 # --------------------------------------------------------------------------- the pipeline
 def track(n1, n2, detector, domainMargin=0, ratio_test=0.7, max_speed=0.5, max_drift=None, psi=200, order=2,
-          device=0, verbose=False, concurrent_detection=False, **detector_kwargs):
+          device=0, verbose=False, concurrent_detection=False, detect_devices=None, **detector_kwargs):
     """Detector -> domain masks -> matcher + ratio mask -> drift mask -> model mask (ftlib.py:259-281).
     Fewer than two key points on either side at any stage ends with four empty arrays.
     ``concurrent_detection``: the two images on two host threads (the package's own detector only: its per-level host
-    work - candidate selection, sorting - then runs beside the other image's kernels; the results do not depend on it)."""
-    def detect(n):
-        kp, descr = detector(n[1], **detector_kwargs)
+    work - candidate selection, sorting - then runs beside the other image's kernels; the results do not depend on it).
+    ``detect_devices``: (GPU of image 1, GPU of image 2), handed to the detector as ``device=`` - with
+    ``concurrent_detection`` the two images are then detected on two GPUs at once; the key points do not depend on it."""
+    def detect(n, dev=None):
+        kw = detector_kwargs if dev is None else dict(detector_kwargs, device=dev)
+        kp, descr = detector(n[1], **kw)
         return kp, np.asarray(descr)
+    devs = (None, None) if detect_devices is None else tuple(detect_devices)
     if concurrent_detection:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=2) as pool:
-            sets = list(pool.map(detect, (n1, n2)))
+            sets = list(pool.map(detect, (n1, n2), devs))
     else:
-        sets = [detect(n1)]
+        sets = [detect(n1, devs[0])]
         if len(sets[0][0]) >= 2:
-            sets.append(detect(n2))
+            sets.append(detect(n2, devs[1]))
     if any(len(kp) < 2 for kp, _ in sets):
         return _EMPTY
     for this, other, (kp, descr) in ((0, n2, sets[0]), (1, n1, sets[1])):
@@ -206,11 +210,23 @@ def lstsq_filter(x1, y1, x2, y2, psi=200, order=2, verbose=False, **kwargs):
 
 def feature_tracking(n1, n2, find_key_points=find_key_points, **kwargs):
     """ftlib.py:241-285: x1, y1, x2, y2 (pixels) of matched and filtered key points of two images.
-    ``kwargs`` are shared by the detector and the filters, as in the reference."""
+    ``kwargs`` are shared by the detector and the filters, as in the reference.
+    ``devices`` (not a reference keyword; the forms of ``pmlib.resolve_devices``): the package's detector finds the key
+    points of image 1 on the first GPU named and those of image 2 on the second (the same, if only one is named), on two
+    threads; the matcher runs on the first.  The result does not depend on it.  A detector passed as
+    ``find_key_points=`` is called as without it."""
     own = ('domainMargin', 'ratio_test', 'max_speed', 'max_drift', 'psi', 'order', 'device', 'verbose')
+    is_own = find_key_points is globals()['find_key_points']
+    detect_devices = None
+    if kwargs.get('devices') is not None:
+        from .pmlib import resolve_devices
+        devs = resolve_devices(kwargs['devices'], kwargs.get('device', 0), _capi.device_count())
+        kwargs = dict(kwargs, device=devs[0])
+        if is_own:
+            detect_devices = (devs[0], devs[1 % len(devs)])
     stage_kw = {k: kwargs[k] for k in own if k in kwargs}
-    det_kw = {k: v for k, v in kwargs.items() if k not in own or k in ('verbose', 'device')}
-    if find_key_points is not globals()['find_key_points']:
+    det_kw = {k: v for k, v in kwargs.items() if (k not in own or k in ('verbose', 'device')) and k != 'devices'}
+    if not is_own:
         det_kw = dict(kwargs)                       # a user detector sees everything, like the reference's call
-    return tuple(track(n1, n2, lambda image, **kw: find_key_points(image, **det_kw),
-                       concurrent_detection=find_key_points is globals()['find_key_points'], **stage_kw))
+    return tuple(track(n1, n2, lambda image, **kw: find_key_points(image, **dict(det_kw, **kw)),
+                       concurrent_detection=is_own, detect_devices=detect_devices, **stage_kw))

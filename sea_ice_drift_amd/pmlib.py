@@ -11,7 +11,13 @@ The structure is  prelude (host, NumPy)  ->  dispatch (GPU)  ->  postlude (host,
                    rotation exactly as pmlib.py:393-428 / :249-324 do;
 * the dispatch replaces the ``multiprocessing.Pool.map`` of pmlib.py:436-448 with the HIP
   kernel behind the C ABI (``_capi``).  ``threads`` is accepted for signature compatibility
-  and ignored.  There is no CPU fallback: without the HIP library / a gfx950 device this
+  and ignored: the parallelism argument here is ``devices=`` (not a reference keyword).  By default one
+  device handle - the one of ``device=`` - runs all points; ``devices='all'``, ``devices=n`` or a
+  sequence of GPU indices cuts the points into one shard of equal estimated run time per handle
+  (``plan_shards``), enqueues every shard from the calling thread and merges the rows back into the
+  original point order - in this process, with no collective, and with the results of the one-handle
+  call bit for bit (a point's result does not depend on which other points share its launch).
+  There is no CPU fallback: without the HIP library / a gfx950 device this
   raises.  Options the kernels do not implement (an ``mtype`` other
   than TM_CCOEFF_NORMED, a user ``template_matcher``, ``img_size`` outside 2..255) raise
   ``NotImplementedError``;
@@ -206,37 +212,46 @@ def _sweep_options(kwargs):
 
 # One device handle per GPU, created on first use and kept (streams, device buffers, the two pair slots).  A handle
 # carries the state of ONE call at a time (current pair, resident points, results), so every use of a shared handle
-# holds that device's lock from the upload to the fetch: concurrent pattern_matching / pm_dispatch calls on one GPU
+# holds that handle's lock from the upload to the fetch: concurrent pattern_matching / pm_dispatch calls on one GPU
 # queue up instead of interleaving (the reference's module globals, pmlib.py:33-34, make it
-# non-re-entrant; here the C ABI is re-entrant per handle and the Python mirror serialises per device).  A caller
+# non-re-entrant; here the C ABI is re-entrant per handle and the Python mirror serialises per handle).  A caller
 # who wants two calls in flight on one GPU passes its own ``context=`` to each.
+# The registry is keyed (device, replica): replica 0 is the handle of every one-handle call; a ``devices=`` list that
+# names a GPU k + 1 times uses replicas 0 .. k of it.
 _CONTEXTS = {}
 _CONTEXT_LOCKS = {}
 _REGISTRY_LOCK = threading.Lock()
 
 
-def _shared_context(device):
-    """(handle, lock) of ``device``.  The lock object of a device is created once and never replaced."""
+def _shared_context(device, replica=0):
+    """(handle, lock) of replica ``replica`` of ``device``.  The lock object of a key is created once and never replaced."""
+    key = (int(device), int(replica))
     with _REGISTRY_LOCK:
-        lock = _CONTEXT_LOCKS.get(device)
+        lock = _CONTEXT_LOCKS.get(key)
         if lock is None:
-            lock = _CONTEXT_LOCKS[device] = threading.RLock()
-        ctx = _CONTEXTS.get(device)
+            lock = _CONTEXT_LOCKS[key] = threading.RLock()
+        ctx = _CONTEXTS.get(key)
         if ctx is None:
-            ctx = _CONTEXTS[device] = _capi.PMContext(device)
+            ctx = _CONTEXTS[key] = _capi.PMContext(key[0])
         return ctx, lock
 
 
-def release_contexts(timeout=5.0):
-    """Destroy the per-device handles (each keeps two image-pair slots resident in HBM) and hand back the cached device
-    memory of the detector, the matcher and the first-guess evaluation.  Registered with atexit; the next call creates a
-    fresh handle.  Every handle is closed under its own device's lock - the one its users hold from upload to fetch - so a
-    call in flight on another thread finishes first; a lock that stays held for ``timeout`` seconds (a worker stuck at
-    interpreter exit) is given up on and its handle left to the process teardown."""
+def resident_handles():
+    """Sorted (device, replica) keys of the shared handles alive in this process."""
     with _REGISTRY_LOCK:
-        items = [(device, ctx, _CONTEXT_LOCKS[device]) for device, ctx in _CONTEXTS.items()]
-        _CONTEXTS.clear()                                             # (the locks stay: a device's lock is never replaced)
-    for device, ctx, lock in items:
+        return sorted(_CONTEXTS)
+
+
+def release_contexts(timeout=5.0):
+    """Destroy the shared handles, every replica of every device (each keeps two image-pair slots resident in HBM), and
+    hand back the cached device memory of the detector, the matcher and the first-guess evaluation.  Registered with
+    atexit; the next call creates a fresh handle.  Every handle is closed under its own lock - the one its users hold from
+    upload to fetch - so a call in flight on another thread finishes first; a lock that stays held for ``timeout`` seconds
+    (a worker stuck at interpreter exit) is given up on and its handle left to the process teardown."""
+    with _REGISTRY_LOCK:
+        items = [(ctx, _CONTEXT_LOCKS[key]) for key, ctx in sorted(_CONTEXTS.items())]
+        _CONTEXTS.clear()                                             # (the locks stay: a key's lock is never replaced)
+    for ctx, lock in items:
         if lock.acquire(timeout=timeout):
             try:
                 ctx.close()
@@ -256,12 +271,199 @@ class _NoLock(object):
         return False
 
 
-def pm_dispatch(img1, img2, c1, r1, c2fg, r2fg, border, img_size, alpha0, device=0, context=None, **kwargs):
+# ------------------------------------------------------------------ several handles in one call
+def _is_index(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def resolve_devices(devices, device, n_visible):
+    """The GPU index of every handle a call uses, from its ``devices=`` argument (pure function):
+
+    ``None``                  -> ``[device]``: the one handle of ``device=`` (``n_visible`` is not looked at);
+    ``'all'``                 -> ``[0 .. n_visible - 1]``;
+    an int ``n``              -> the first ``n`` visible GPUs, ``1 <= n <= n_visible``;
+    a sequence of GPU indices -> one handle per entry; an index may repeat (``[0, 0]``: two handles on GPU 0).
+
+    Anything else - a bool, another string, a negative index, an index >= ``n_visible``, an empty sequence - is a
+    ``ValueError`` that names the offending entry."""
+    if devices is None:
+        return [int(device)]
+    n_visible = int(n_visible)
+    if isinstance(devices, str):
+        if devices != 'all':
+            raise ValueError("devices=%r: the only string form is 'all'" % (devices,))
+        if n_visible < 1:
+            raise ValueError("devices='all': no GPU is visible")
+        return list(range(n_visible))
+    if isinstance(devices, (bool, np.bool_)):
+        raise ValueError('devices=%r: a bool is neither a count nor a list of GPU indices' % (devices,))
+    if _is_index(devices):
+        if not 1 <= devices <= n_visible:
+            raise ValueError('devices=%d: the number of GPUs must lie in 1..%d (the visible ones)' % (devices, n_visible))
+        return list(range(int(devices)))
+    if isinstance(devices, np.ndarray) and devices.ndim != 1:
+        raise ValueError('devices=%r: not a flat sequence of GPU indices' % (devices,))
+    if not isinstance(devices, (list, tuple, range, np.ndarray)):
+        raise ValueError("devices=%r: expected None, 'all', a count or a sequence of GPU indices" % (devices,))
+    if len(devices) == 0:
+        raise ValueError('devices=%r: an empty sequence names no GPU' % (devices,))
+    for k, d in enumerate(devices):
+        if not _is_index(d):
+            raise ValueError('devices[%d]=%r is not a GPU index (an int)' % (k, d))
+        if not 0 <= d < n_visible:
+            raise ValueError('devices[%d]=%d: GPU indices lie in 0..%d (%d visible)' % (k, d, n_visible - 1, n_visible))
+    return [int(d) for d in devices]
+
+
+def plan_shards(border, n_shards, img_size, n_angles, flags):
+    """The points of a call cut into ``n_shards`` shards of equal estimated run time: a list of ``n_shards`` ascending
+    int64 index arrays that partition ``range(N)``.  The cost model is the library's, through ``dist.shard_cuts_by_cost``
+    (the cuts of the multi-process path: contiguous runs of the border-ordered points, so a handle holds one or two
+    launch classes).  A shard may be empty when ``N < n_shards``.  Pure function of its arguments."""
+    from sea_ice_drift_amd import dist
+    border = np.asarray(border, dtype=np.float64).ravel()
+    n_shards = int(n_shards)
+    if n_shards < 1:
+        raise ValueError('n_shards=%d: at least one shard' % n_shards)
+    if n_shards == 1:
+        return [np.arange(border.size, dtype=np.int64)]
+    order, cuts, _ = dist.shard_cuts_by_cost(border, n_shards, img_size, n_angles, flags)
+    return [dist.indices_of_cut(order, cuts, k).astype(np.int64, copy=False) for k in range(n_shards)]
+
+
+class _Handles(object):
+    """The shared handles of a multi-device call, locked for the length of a ``with`` block: the k-th repeat of a GPU in
+    ``devs`` is replica k of it.  The locks are taken in sorted key order - two concurrent calls, whatever the order of
+    their lists, cannot hold one lock each and wait for the other's - and before the handles are looked up, so a handle
+    is never one that ``release_contexts`` is closing."""
+
+    def __init__(self, devs):
+        seen, self.keys = {}, []
+        for d in devs:
+            self.keys.append((d, seen.get(d, 0)))
+            seen[d] = seen.get(d, 0) + 1
+        self._held = []
+
+    def __enter__(self):
+        try:
+            for key in sorted(self.keys):
+                with _REGISTRY_LOCK:
+                    lock = _CONTEXT_LOCKS.setdefault(key, threading.RLock())
+                lock.acquire()
+                self._held.append(lock)
+            return [_shared_context(*key)[0] for key in self.keys]
+        except BaseException:
+            self.__exit__()
+            raise
+
+    def __exit__(self, *a):
+        while self._held:
+            self._held.pop().release()
+        return False
+
+
+def _upload_to_all(ctxs, img1, img2):
+    """Start the upload of the pair to every handle; returns a function that waits for ALL of them and then re-raises
+    the first error (no copy is left running into a handle whose lock the caller is about to release)."""
+    pending, first = [], None
+    try:
+        for ctx in ctxs:
+            pending.append(ctx.upload_pair_background(img1, img2))
+    except BaseException as e:                                        # noqa: re-raised by wait()
+        first = e
+
+    def wait():
+        err = first
+        for p in pending:
+            try:
+                p.wait()
+            except BaseException as e:                                # noqa: the other uploads are still joined
+                err = err or e
+        if err is not None:
+            raise err
+    return wait
+
+
+def _dispatch_sharded(ctxs, c1, r1, c2fg, r2fg, border, img_size, alpha0, angles, flags, rot, timings=None):
+    """N points over the handles ``ctxs`` (locked by the caller, the pair resident on each) -> (N,5) float64 in the
+    original point order.  Every non-empty shard is given to its handle and started from the calling thread - ``run``
+    only enqueues - and then the shards are fetched one after the other.  If anything raises, the handles that were
+    given work are synchronised before the exception leaves: no launch is in flight on a handle once its lock is free.
+    ``timings``: a dict that receives the seconds spent in the shard plan, set_points, run (enqueue), the wait for the
+    kernels, fetch and merge (tools/multi_device_bench.py); the wait is then a ``sync`` of its own before each fetch."""
+    v = [np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (c1, r1, c2fg, r2fg, border)]
+    n = v[0].size
+    if any(x.size != n for x in v):
+        raise ValueError('point vectors differ in length')
+    if n == 0:
+        return np.zeros((0, 5))
+    clock = time.perf_counter
+    t = dict(plan=0.0, set_points=0.0, run=0.0, kernel_wait=0.0, fetch=0.0, merge=0.0)
+    out = np.empty((n, 5), dtype=np.float64)
+    started, done = [], 0
+    try:
+        t0 = clock()
+        shards = plan_shards(v[4], len(ctxs), img_size, len(angles), flags)
+        t['plan'] = clock() - t0
+        for ctx, idx in zip(ctxs, shards):
+            if idx.size == 0:
+                continue
+            started.append((ctx, idx))
+            t0 = clock()
+            ctx.set_points(*[x[idx] for x in v], img_size, alpha0, angles, rot=rot, flags=flags)
+            t1 = clock()
+            ctx.run()
+            t['set_points'] += t1 - t0
+            t['run'] += clock() - t1
+        for ctx, idx in started:
+            t0 = clock()
+            if timings is not None:
+                ctx.sync()
+            t1 = clock()
+            rows = ctx.fetch(want_ij=False)
+            t2 = clock()
+            out[idx] = rows
+            done += 1
+            t['kernel_wait'] += t1 - t0
+            t['fetch'] += t2 - t1
+            t['merge'] += clock() - t2
+    except BaseException as e:
+        for ctx, _ in started[done:]:
+            try:
+                ctx.sync()
+            except Exception:                                         # noqa: the first error is the one reported
+                pass
+        if isinstance(e, _capi.SidPmError) and e.code == -4:
+            raise NotImplementedError(str(e))
+        raise
+    if timings is not None:
+        timings.update(t, points_per_handle=[int(idx.size) for idx in shards])
+    return out
+
+
+def pm_dispatch(img1, img2, c1, r1, c2fg, r2fg, border, img_size, alpha0, device=0, context=None, devices=None, timings=None,
+                **kwargs):
     """The batch seam (reference pmlib.py:436-448): N points -> (N,5) float64 on the GPU.
     ``context``: a PMContext to run on; by default one handle per device is created on first use and reused, so
-    that repeated calls pay neither for streams and events nor for device buffers again."""
+    that repeated calls pay neither for streams and events nor for device buffers again.
+    ``devices``: ``None`` (the one handle of ``device``), ``'all'``, a count or a sequence of GPU indices
+    (``resolve_devices``): with more than one handle the points are sharded over them (``plan_shards``) and the rows
+    merged back; the result equals the one-handle call's bit for bit.  ``img1`` = None then means that an earlier call
+    with the same ``devices`` left the pair resident on these handles.  Not together with ``context``.
+    ``timings``: a dict that a call on several handles fills with the seconds of its stages (``_dispatch_sharded``)."""
     angles, flags = _sweep_options(kwargs)
     rot = rotation_table(angles, alpha0, img_size)
+    if devices is not None:
+        if context is not None:
+            raise ValueError('devices= and context= exclude each other: a context is one handle')
+        devs = resolve_devices(devices, device, _capi.device_count())
+        if len(devs) > 1:
+            with _Handles(devs) as ctxs:
+                if img1 is not None:
+                    _upload_to_all(ctxs, img1, img2)()
+                return _dispatch_sharded(ctxs, c1, r1, c2fg, r2fg, border, img_size, alpha0, angles, flags, rot,
+                                         timings=timings)
+        device = devs[0]                    # one handle: the code path of devices=None
     ctx, lock = _shared_context(device) if context is None else (context, _NoLock())
     with lock:
         if img1 is not None:                # (None: the caller uploaded the pair to ``context`` already)
@@ -375,10 +577,26 @@ def pattern_matching(lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2,
         prelude with both paths, tests/test_gpu_first_guess.py the flagging).  A triangulation with a degenerate simplex
         and ``old_border=False`` (unrounded values) are evaluated by SciPy alone.
     ``device`` (GPU index, default 0) and ``context`` (a ``_capi.PMContext`` of the caller's, for two calls in flight on
-        one GPU)."""
+        one GPU).
+    ``devices`` = None (default: the one handle of ``device``) | 'all' | a count | a sequence of GPU indices, e.g.
+        ``[0, 1, 2, 3]`` (``resolve_devices``).  With several handles the pair is uploaded to each of them while the host
+        works on the first guess (evaluated on the first entry), the valid grid points are cut into one shard of equal
+        estimated run time per handle (``plan_shards``) and every handle runs its shard; the seven grids equal those of the
+        one-handle call bit for bit.  ``threads``, the reference's parallelism argument, stays accepted and ignored."""
     t0 = time.time()
     img1, img2 = n1[1], n2[1]
     _sweep_options(kwargs)                                            # unsupported options fail before any work
+    devices = kwargs.pop('devices', None)
+    if devices is not None:
+        if kwargs.get('context') is not None:
+            raise ValueError('devices= and context= exclude each other: a context is one handle')
+        devs = resolve_devices(devices, kwargs.get('device', 0), _capi.device_count())
+        kwargs['device'] = devs[0]                                    # the first guess, and the handle if there is but one
+        if len(devs) > 1:
+            kwargs.pop('context', None)
+            pre, results = _pattern_matching_sharded(devs, lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2, margin, img_size, kwargs)
+            print('\n', 'Pattern matching - OK! (%3.0f sec)' % (time.time() - t0))
+            return pm_postlude(pre, results, n2, srs=srs)
     # The image pair goes to the device while the host works on the first guess (its Delaunay triangulation is the
     # longest step of the prelude): the upload is a C call that does not hold the interpreter lock.
     ctx = kwargs.pop('context', None)
@@ -397,3 +615,22 @@ def pattern_matching(lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2,
             results = np.zeros((0, 5))
     print('\n', 'Pattern matching - OK! (%3.0f sec)' % (time.time() - t0))
     return pm_postlude(pre, results, n2, srs=srs)
+
+
+def _pattern_matching_sharded(devs, lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2, margin, img_size, kwargs):
+    """The middle of ``pattern_matching`` on several handles -> (prelude, (N,5) results).  The handles are this call's from
+    the uploads to the last fetch; all uploads are started before the host prelude and waited for before the first
+    ``set_points``."""
+    angles, flags = _sweep_options(kwargs)
+    with _Handles(devs) as ctxs:
+        wait = _upload_to_all(ctxs, n1[1], n2[1])
+        try:
+            pre = pm_prelude(lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2, margin=margin, img_size=img_size, **kwargs)
+        finally:
+            wait()                                                    # (re-raises what an upload raised)
+        gpi = pre['gpi']
+        if not gpi.any():
+            return pre, np.zeros((0, 5))
+        rot = rotation_table(angles, pre['alpha0'], img_size)
+        return pre, _dispatch_sharded(ctxs, pre['c1pm1i'][gpi], pre['r1pm1i'][gpi], pre['c2fg'][gpi], pre['r2fg'][gpi],
+                                      pre['brd2'][gpi], img_size, pre['alpha0'], angles, flags, rot)

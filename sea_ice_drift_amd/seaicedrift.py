@@ -15,7 +15,9 @@ from sea_ice_drift_amd.pmlib import pattern_matching
 class SeaIceDrift(object):
     """Retrieve sea ice drift with pattern matching on an MI355X."""
 
-    def __init__(self, n1, n2, **kwargs):
+    def __init__(self, n1, n2, devices=None, **kwargs):
+        """``devices``: the GPUs that ``get_drift_FT`` and ``get_drift_PM`` use unless a call names its own - None (one
+        handle, GPU ``device=`` of the call), 'all', a count or a sequence of GPU indices (``pmlib.resolve_devices``)."""
         for n in (n1, n2):
             if isinstance(n, str):
                 raise NotImplementedError(
@@ -24,14 +26,19 @@ class SeaIceDrift(object):
                     'or wrap uint8 arrays in sea_ice_drift_amd.domain.ArrayNansat')
         self.n1 = n1
         self.n2 = n2
+        self.devices = devices
 
     def get_drift_FT(self, **kwargs):
         """Same returns as the reference (seaicedrift.py:42-60): u, v, lon1, lat1, lon2, lat2 of the matched
         key points.  Detection and matching run on the GPU (``sea_ice_drift_amd.orb``, ``include/sid_ft.h``), the
         filters on the host; ``find_key_points=`` takes another detector (see ``ftlib.feature_tracking``).  ``nsr=``
-        selects the units of u, v as in the reference (``lib.get_drift_vectors``)."""
+        selects the units of u, v as in the reference (``lib.get_drift_vectors``).  ``devices=`` (or the constructor's): the
+        key points of image 1 on its first GPU, those of image 2 on its second (``ftlib.feature_tracking``)."""
+        if self.devices is not None:
+            kwargs.setdefault('devices', self.devices)
         x1, y1, x2, y2 = feature_tracking(self.n1, self.n2, **kwargs)
         kwargs.pop('find_key_points', None)
+        kwargs.pop('devices', None)
         out = get_drift_vectors(self.n1, x1, y1, self.n2, x2, y2, **kwargs)
         self._prefetch_first_guess(out[2], out[3])
         return out
@@ -56,7 +63,10 @@ class SeaIceDrift(object):
 
     def get_drift_PM(self, lons, lats, lon1, lat1, lon2, lat2, **kwargs):
         """Same arguments and returns as the reference (seaicedrift.py:62-88):
-        u, v, a, r, h, lon2_dst, lat2_dst on the (lons, lats) grid."""
+        u, v, a, r, h, lon2_dst, lat2_dst on the (lons, lats) grid.  ``devices=`` (or the constructor's) spreads the grid
+        points over several GPUs (``pmlib.pattern_matching``)."""
+        if self.devices is not None:
+            kwargs.setdefault('devices', self.devices)
         x1, y1 = self.n1.transform_points(lon1, lat1, 1)
         x2, y2 = self.n2.transform_points(lon2, lat2, 1)
         return pattern_matching(lons, lats, self.n1, x1, y1, self.n2, x2, y2, **kwargs)
