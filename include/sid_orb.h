@@ -13,10 +13,11 @@
  *
  *   pyramid      n_levels levels, level l = level 0 resampled by 1 / scale^l (scale 1.2): 16.16 fixed-point source
  *                coordinates, 8-bit bilinear weights, round half up
- *   corners      FAST-9 on the 16-pixel Bresenham ring of radius 3 (threshold fast_threshold), score = the largest
- *                threshold that still passes; 3x3 non-maximum suppression (strictly greater than all 8 neighbours)
+ *   corners      FAST-9 on the 16-pixel Bresenham ring of radius 3 (threshold fast_threshold), score = the smallest
+ *                threshold that no longer passes (the scores only rank neighbours); 3x3 non-maximum suppression (strictly greater than all 8 neighbours)
  *   ranking      Harris response on a 7x7 block with central differences, 25 (ab - c^2) - (a + b)^2 in int64
- *                (k = 0.04); the best n_l per level, n_l from OpenCV's geometric split of n_features
+ *                (k = 0.04); the best n_l per level, n_l from OpenCV's geometric split of n_features, each share
+ *                capped by what the levels before it left of n_features (the n_l sum to n_features exactly)
  *   orientation  intensity centroid (m10, m01) over the disc of radius patch_size / 2, quantised to 32 directions by
  *                integer dot products with a host-built direction table
  *   descriptor   256 intensity comparisons on a 5x5-binomial-smoothed level image; the pair pattern (seeded, within

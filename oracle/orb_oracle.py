@@ -25,7 +25,9 @@ def level_geometry(rows, cols, n_levels, scale_factor, n_features):
     nd = n_features * (1.0 - factor) / (1.0 - factor ** n_levels)
     want, tot = [], 0
     for _ in range(n_levels - 1):
-        want.append(int(np.floor(nd + 0.5)))
+        # (never more than what is left of n_features: the rounded shares of many levels can add up to a few more, and
+        # n_features is an upper bound - include/sid_orb.h)
+        want.append(min(int(np.floor(nd + 0.5)), n_features - tot))
         tot += want[-1]
         nd *= factor
     want.append(max(n_features - tot, 0))

@@ -664,6 +664,7 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
     uint8_t *d_img0 = nullptr, *d_lvl = nullptr, *d_aux = nullptr, *d_desc = nullptr;
     Cand *d_cand = nullptr, *d_sel = nullptr; unsigned int *d_count = nullptr, *d_hist = nullptr;
     float *d_xy = nullptr; long long *d_resp = nullptr; DState *d_state = nullptr; unsigned int *d_rank = nullptr;
+    // (both sides of this bound: tests/test_gpu_orb_edges.py::test_equal_responses_on_either_side_of_the_selection_buffer)
     const unsigned int sel_cap = (unsigned int)std::min<int64_t>((int64_t)4 * (int64_t)P->n_features + 65536, (int64_t)1 << 26);
     int8_t *d_pat = nullptr; int32_t *d_dirs = nullptr, *d_kp = nullptr, *d_dir = nullptr;
     std::vector<Cand> cand;
@@ -679,7 +680,9 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
             const double factor = 1.0 / (double)P->scale_factor;
             double nd = (double)P->n_features * (1.0 - factor) / (1.0 - pow(factor, (double)L));
             int sum = 0;
-            for (int l = 0; l < L - 1; ++l) { want[l] = (int)floor(nd + 0.5); sum += want[l]; nd *= factor; }
+            // (a share never exceeds what is left of n_features: the rounded shares of many levels can add up to a few more than
+            // n_features - 4 for n_features = 3 on 5 levels of scale 1.05 - and the key-point buffers hold n_features)
+            for (int l = 0; l < L - 1; ++l) { want[l] = std::min((int)floor(nd + 0.5), P->n_features - sum); sum += want[l]; nd *= factor; }
             want[L - 1] = std::max(P->n_features - sum, 0);
         }
         const size_t area0 = (size_t)rows * cols;

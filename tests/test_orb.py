@@ -92,7 +92,8 @@ def test_selection_and_ordering_on_the_device_equal_the_host_route(monkeypatch):
     """Round 4: the levels run on the device from end to end (radix selection of the level's share by a one-wavefront pick,
     exact (response, y, x) order by counting) with one synchronisation per image; SID_ORB_HOST_SELECT=1 is the previous route
     (counts and histograms to the host, std::sort there).  Same key points in the same order, bit for bit - more features than
-    candidates, fewer, a cap by max_out, plateaus of equal responses - and both equal the oracle."""
+    candidates, fewer, plateaus of equal responses - and both equal the oracle.  (max_out equals n_features here, as in every
+    call through the Python wrapper: a cap by max_out is tested in tests/test_gpu_orb_edges.py::test_max_out_keeps_a_prefix.)"""
     rng = np.random.default_rng(8)
     big = syn.make_pair(1500, 1300, seed=33)[1]
     flat = np.full((600, 600), 90, dtype=np.uint8)
