@@ -99,7 +99,7 @@ struct Geo {
     int gpitch, arow0, tab_rows, ones_slot;   // operand-table geometry (mfma_lds_layout) and the all-ones slot: 15, or 7 paired
     int win_off, sii_off, u_off, patch_off, ppitch, pdim, pradius, queue_off, trow_bytes;
     int pr0, pc0;                    // patch origin on image 1
-    u32 win_magic;                   // floor(2^32 / (wpitch/4)) + 1: idx / (wpitch/4) == umulhi(idx, win_magic) for idx < 2^16
+    u32 win_magic;                   // floor(2^32 / dwr) + 1, dwr = (ww + 3) / 4 the pixel dwords of a window row: idx / dwr == umulhi(idx, win_magic) for idx < 2^16
     u32 patch_magic, rw_magic;       // same for ppitch/4 and for rw
     int band;                        // output rows per sweep work item (kernel template parameter)
     int wp_off, wp_pitch, wp_rows, strip_off, wrows, npair, nsingle;   // row-pair kernel (RpLdsLayout)
@@ -484,7 +484,9 @@ __device__ __noinline__ void ph_window_t(const uint8_t *img2, long long rows2, l
         const int pst = (int)stride1;
         const uint8_t *porg = img1 + (long long)G.pr0 * stride1 + G.pc0;
         const u32 pmis = (u32)(reinterpret_cast<uintptr_t>(porg) & 3);
-        const uint8_t *porg4 = porg - pmis;
+        const uintptr_t porg4u = reinterpret_cast<uintptr_t>(porg) - pmis;                       // (scalar, as the window's origin below)
+        const uint8_t *porg4 = reinterpret_cast<const uint8_t *>(((uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(porg4u >> 32)) << 32) |
+                                                                 (uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)porg4u));
         const long long plast_ll = (long long)((reinterpret_cast<uintptr_t>(img1 + (rows1 - 1) * stride1 + cols1) - 1) & ~(uintptr_t)3) -
                                    (long long)reinterpret_cast<uintptr_t>(porg4);
         const u32 plast = plast_ll > 0x7ffffff0ll ? 0x7ffffff0u : (u32)plast_ll;
@@ -504,46 +506,75 @@ __device__ __noinline__ void ph_window_t(const uint8_t *img2, long long rows2, l
     }
     uint8_t *win = smem + G.win_off;
     const int wpitch = G.wpitch, ww = G.ww, wh = G.wh;
-    const int dw_per_row = wpitch >> 2, ndw = (wh + G.band - 1) * dw_per_row;   // + band-1 zero rows below
-    const u32 magic = G.win_magic;
+    // Only the dwords that hold pixels are loaded: dwr per window row.  The rest of the pitch (the class pitch of the row-pair
+    // kernels is 104 .. 136 bytes for 75 .. 107 pixels) and the band - 1 zero rows below the window are plain LDS stores.
+    const int dw_per_row = wpitch >> 2, dwr = (ww + 3) >> 2, ndw = wh * dwr;
+    const u32 magic = G.win_magic;                                     // idx / dwr
     const int st = (int)stride2;
     // all addresses as 32-bit offsets from the (dword-aligned) window origin: no 64-bit multiplies, no divisions
     const uint8_t *org = img2 + G.r0 * stride2 + G.c0;
     const u32 mis = (u32)(reinterpret_cast<uintptr_t>(org) & 3);
-    const uint8_t *org4 = org - mis;
+    // (the origin is the same for every thread: kept in scalar registers, so that a load is "scalar base + 32-bit lane offset"
+    // and costs no 64-bit address arithmetic per dword)
+    const uintptr_t org4u = reinterpret_cast<uintptr_t>(org) - mis;
+    const uint8_t *org4 = reinterpret_cast<const uint8_t *>(((uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(org4u >> 32)) << 32) |
+                                                            (uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)org4u));
     const long long last_ll = (long long)((reinterpret_cast<uintptr_t>(img2 + (rows2 - 1) * stride2 + cols2) - 1) & ~(uintptr_t)3) -
                               (long long)reinterpret_cast<uintptr_t>(org4);
     const u32 last_off = last_ll > 0x7ffffff0ll ? 0x7ffffff0u : (u32)last_ll;  // offset of the last legal dword
-    // kWin dwords per thread and round trip: the common small windows (border <= 23 at 256 threads) load in
-    // one trip, i.e. one HBM/L2 latency per point
+    // kWin dwords per thread and round trip: the common small windows (border <= 23 at 192 threads, <= 32 at 256) load in
+    // one trip, i.e. one HBM/L2 latency per point.  A slot no thread of the workgroup has a dword for is skipped (uniform).
     constexpr int kWin = KWIN;
+    const u32 tailmask = (ww & 3) ? (1u << (8 * (ww & 3))) - 1u : 0xffffffffu;
     for (int base = 0; base < ndw; base += kWin * kBlockM) {
-        u32 lo[kWin], hi[kWin], shv[kWin];
-        int rowv[kWin], dqv[kWin];
+        u32 lo[kWin], hi[kWin], shv[kWin], mskv[kWin];
+        int dstv[kWin];
 #pragma unroll
         for (int u = 0; u < kWin; ++u) {
-            const int idx = base + u * kBlockM + tid;
-            const int idc = idx < ndw ? idx : 0;
-            const int row = (int)__umulhi((u32)idc, magic);
-            const int dq = idc - row * dw_per_row;
-            rowv[u] = row; dqv[u] = dq;
-            const int rc = row < wh ? row : wh - 1;                    // clamp so that the loads are always legal
-            const int dqc = 4 * dq < ww ? dq : 0;
-            const u32 o = (u32)(rc * st + 4 * dqc) + mis;
-            const u32 oa = o & ~3u;
-            const u32 ob = oa + 4 <= last_off ? oa + 4 : last_off;
-            shv[u] = o & 3u;
-            lo[u] = SID_IMG_LOAD(reinterpret_cast<const u32 *>(org4 + oa));
-            hi[u] = SID_IMG_LOAD(reinterpret_cast<const u32 *>(org4 + ob));
+            if (base + u * kBlockM < ndw) {
+                const int idx = base + u * kBlockM + tid;
+                const int idc = idx < ndw ? idx : 0;
+                const int row = (int)__umulhi((u32)idc, magic);
+                const int dq = idc - row * dwr;
+                dstv[u] = row * dw_per_row + dq;
+                mskv[u] = dq == dwr - 1 ? tailmask : 0xffffffffu;      // (every task holds a pixel; the last of a row ww & 3 of them)
+                // the dword that holds the task's first pixel lies inside the image; the one behind it is clamped to the
+                // last dword that does (its bytes are then shifted out or masked)
+                const u32 o = (u32)(row * st + 4 * dq) + mis;
+                const u32 oa = o & ~3u;
+                const u32 ob = oa + 4 <= last_off ? oa + 4 : last_off;
+                shv[u] = o & 3u;
+                lo[u] = SID_IMG_LOAD(reinterpret_cast<const u32 *>(org4 + oa));
+                hi[u] = SID_IMG_LOAD(reinterpret_cast<const u32 *>(org4 + ob));
+            }
+        }
+        if (base == 0) {
+            // zeros, while the loads are in flight.  Behind the pixels of every row: thread = row, its dw_per_row - dwr dwords as
+            // one ds_write_b32 (odd dwr) and ds_write_b64 (row-pair kernels: dw_per_row is even); the rows below the window: one run of
+            // ds_write_b64, taken from the last thread down (the rows' threads are the first ones)
+            const int npad = dw_per_row - dwr;
+            const bool p8 = (dw_per_row & 1) == 0;                     // (the classic kernels' pitch is a multiple of 4 only: dword stores)
+            for (int row = tid; row < wh; row += kBlockM) {
+                u32 *p = reinterpret_cast<u32 *>(win) + row * dw_per_row + dwr;
+                int k = 0;
+                if (p8 && (dwr & 1)) { if (npad > 0) p[0] = 0u; k = 1; }
+                if (p8) for (; k + 1 < npad; k += 2) *reinterpret_cast<uint2 *>(p + k) = make_uint2(0u, 0u);
+                else for (; k < npad; ++k) p[k] = 0u;
+            }
+            const int nzd = (G.band - 1) * dw_per_row;
+            if (p8) {
+                uint2 *z = reinterpret_cast<uint2 *>(win + wh * wpitch);
+                for (int i = kBlockM - 1 - tid; i < (nzd >> 1); i += kBlockM) z[i] = make_uint2(0u, 0u);
+            } else {
+                u32 *z = reinterpret_cast<u32 *>(win + wh * wpitch);
+                for (int i = kBlockM - 1 - tid; i < nzd; i += kBlockM) z[i] = 0u;
+            }
         }
 #pragma unroll
         for (int u = 0; u < kWin; ++u) {
-            const int idx = base + u * kBlockM + tid;
-            if (idx < ndw) {
-                u32 v = __builtin_amdgcn_alignbyte(hi[u], lo[u], shv[u]) ^ 0x80808080u;
-                const int nvalid = rowv[u] < wh ? ww - 4 * dqv[u] : 0;
-                if (nvalid < 4) v = nvalid > 0 ? (v & ((1u << (8 * nvalid)) - 1u)) : 0u;
-                reinterpret_cast<u32 *>(win)[idx] = v;                 // idx == row * dw_per_row + dq
+            if (base + u * kBlockM < ndw) {
+                const int idx = base + u * kBlockM + tid;
+                if (idx < ndw) reinterpret_cast<u32 *>(win)[dstv[u]] = (__builtin_amdgcn_alignbyte(hi[u], lo[u], shv[u]) ^ 0x80808080u) & mskv[u];
             }
         }
     }
@@ -1878,7 +1909,7 @@ __global__ __launch_bounds__(BAND == 8 ? 512 : kMaxBlockM, BAND == 8 ? 2 : kOccM
         G->ppitch = L.ppitch; G->pdim = L.pdim; G->pradius = L.pradius; G->queue_off = L.queue_off;
         G->trow_bytes = L.trow_bytes;
         G->pr0 = (int)floor(r1) - L.pradius; G->pc0 = (int)floor(c1) - L.pradius;
-        G->win_magic = 0xffffffffu / (u32)(L.wpitch >> 2) + 1u; G->patch_magic = 0xffffffffu / (u32)(L.ppitch >> 2) + 1u;
+        G->win_magic = 0xffffffffu / (u32)((ww + 3) >> 2) + 1u; G->patch_magic = 0xffffffffu / (u32)(L.ppitch >> 2) + 1u;
         G->rw_magic = 0xffffffffu / (u32)rw + 1u;
         G->r0 = r0; G->c0 = c0; G->c1 = c1; G->r1 = r1; G->nd = (double)(s * s);
         G->hist_off = 0; G->lin = (int)((A.flags >> 3) & 7u); G->pre = A.pre ? (unsigned long long)(A.pre + (size_t)pt * K * s * s) : 0ull;

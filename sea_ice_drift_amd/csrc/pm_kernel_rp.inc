@@ -193,58 +193,146 @@ __device__ __forceinline__ void sii_put(u32 *base, int idx, u32 v)
 
 // ---------------------------------------------------------------------------------------------
 // S_II' = box sums of w'^2: running sums along the rows into LDS, then down the columns into `out` - LDS (sii_off) or, in
-// the gs instantiations, GLOBAL memory (PMArgs::gsii).  The second pass has one thread per column and run of rows, so the
-// lanes of a wavefront write consecutive placements: coalesced stores.  The global values are read back by this workgroup
+// the gs instantiations, GLOBAL memory (PMArgs::gsii).  The second pass has one thread per column pair and run of rows, so
+// the lanes of a wavefront write consecutive placements: coalesced stores.  The global values are read back by this workgroup
 // only (scoring of the sweep, the winner's matrix), from L2.  In LDS they are the largest item of a point with a large border
 // (42 KB at border 50) and what decides the residency class of most borders above 27 (rp_lds_layout).
+//
+// Both passes work on tasks of a COMPILE-TIME length (straight-line code, every LDS offset an immediate or one scalar
+// multiple of the row pitch): a task fetches everything it needs with wide reads issued up front, then works in registers -
+// no output waits on an LDS round trip of its own (the form of rounds 2-7 read two bytes, or two dwords, per output and
+// waited for them: ~21 dependent round trips per thread and pass at border 20).
+//   rows:    task = (window row y, SEG placements from x = SEG seg, SEG a multiple of 8): SEG + s - 1 bytes as ds_read_b64,
+//            the first sum as v_dot4_i32_i8 of whole dwords, then one square in and one out per placement.  The last segment
+//            of a row may hang over rw: it reads on into bytes the window phase wrote (zeros, the next rows - the window
+//            has three rows or more below its last) and stores under a mask; tasks are numbered segment by segment, so
+//            that only the wavefronts of the last segment run the masked stores.
+//   columns: task = (placement columns x, x + 1; SEGR output rows).  The last segment of a column is pulled up so that it
+//            ends on the last output row, and the last pair of an odd rw back by one column (both recompute values another
+//            task stores as well: the same integers), so no read leaves the rh + s - 1 = wh rows of row sums and no
+//            store needs a mask.
+// The lengths are chosen per point (wavefront-uniform) as those that issue the fewest wavefront-instructions: whole
+// wavefronts of tasks x instructions per task.  The kernels are bound by instruction issue (DESIGN.md section 5.1), so a
+// long task in one wavefront beats short tasks in all of them, whose first sums - s terms for every segment - repeat.
 // ---------------------------------------------------------------------------------------------
-template <bool GS, bool BIG = false>
+template <int S, int SEG>
+__device__ __forceinline__ void rp_sums_row_task(const uint8_t *src, u32 *dst, int nvalid)
+{
+    static_assert(SEG % 8 == 0 && SEG + S - 1 <= 72, "segments start on 8-byte boundaries; 18 dwords per task at most");
+    constexpr int NQ = (SEG + S - 1 + 7) / 8;
+    u32 d[2 * NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) { const uint2 t = reinterpret_cast<const uint2 *>(src)[q]; d[2 * q] = t.x; d[2 * q + 1] = t.y; }
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < S / 4; ++j) c = __builtin_amdgcn_sdot4((int)d[j], (int)d[j], c, false);
+    if (S & 3) { const int t = (int)(d[S / 4] & ((1u << (8 * (S & 3))) - 1u)); c = __builtin_amdgcn_sdot4(t, t, c, false); }
+    u32 o[SEG];
+    o[0] = (u32)c;
+#pragma unroll
+    for (int k = 1; k < SEG; ++k) {                                    // (k is a constant after unrolling: v_bfe_i32 / SDWA selects)
+        const int bi = k + S - 1, bo = k - 1;
+        const int vi = (int)(d[bi >> 2] << (24 - 8 * (bi & 3))) >> 24, vo = (int)(d[bo >> 2] << (24 - 8 * (bo & 3))) >> 24;
+        c += vi * vi - vo * vo;
+        o[k] = (u32)c;
+    }
+    if (nvalid >= SEG) {
+#pragma unroll
+        for (int k = 0; k < SEG; ++k) dst[k] = o[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < SEG; ++k) if (k < nvalid) dst[k] = o[k];
+    }
+}
+
+template <int S, int SEG>
+__device__ __forceinline__ void rp_sums_rows(const uint8_t *win, u32 *rowsum, int wh, int rw, int wpitch)
+{
+    const int tid = threadIdx.x;
+    const int nseg = (rw + SEG - 1) / SEG, ntask = wh * nseg;
+    const u32 magic = 0xffffffffu / (u32)wh + 1u;                      // task / wh == umulhi(task, magic): task < 2^16
+    for (int task = tid; task < ntask; task += kBlockM) {
+        const int seg = (int)__umulhi((u32)task, magic), y = task - seg * wh, xa = seg * SEG;
+        rp_sums_row_task<S, SEG>(win + y * wpitch + xa, rowsum + y * rw + xa, rw - xa);
+    }
+}
+
+template <int S, int SEGR, bool GS>
+__device__ __forceinline__ void rp_sums_col_task(const u32 *col, int rw, u32 *gs, int o0)
+{
+    // rows 0 .. SEGR-2 leave the running sum, rows S .. S+SEGR-2 enter it; the rows between are only part of the first sum
+    u32 a0 = 0, a1 = 0, out0[SEGR > 1 ? SEGR - 1 : 1], out1[SEGR > 1 ? SEGR - 1 : 1], in0[SEGR > 1 ? SEGR - 1 : 1], in1[SEGR > 1 ? SEGR - 1 : 1];
+#pragma unroll
+    for (int i = 0; i < S + SEGR - 1; ++i) {
+        const u32 v0 = col[i * rw], v1 = col[i * rw + 1];
+        if (i < S) { a0 += v0; a1 += v1; }
+        if (i < SEGR - 1) { out0[i] = v0; out1[i] = v1; }
+        if (i >= S) { in0[i - S] = v0; in1[i - S] = v1; }
+    }
+    static_assert(SEGR - 1 <= S, "a row leaves the sum or enters it, not both");
+    u32 r0[SEGR], r1[SEGR];
+    r0[0] = a0; r1[0] = a1;
+#pragma unroll
+    for (int k = 1; k < SEGR; ++k) {
+        a0 += in0[k - 1] - out0[k - 1]; a1 += in1[k - 1] - out1[k - 1];
+        r0[k] = a0; r1[k] = a1;
+    }
+#pragma unroll
+    for (int k = 0; k < SEGR; ++k) { sii_put(gs, o0 + k * rw, r0[k]); sii_put(gs, o0 + k * rw + 1, r1[k]); }
+}
+
+template <int S, int SEGR, bool GS>
+__device__ __forceinline__ void rp_sums_cols(const u32 *rowsum, u32 *gs, int rh, int rw)
+{
+    const int tid = threadIdx.x;
+    const int npr = (rw + 1) >> 1, nseg = (rh + SEGR - 1) / SEGR, ntask = npr * nseg;
+    const u32 magic = 0xffffffffu / (u32)npr + 1u;
+    for (int task = tid; task < ntask; task += kBlockM) {
+        const int seg = (int)__umulhi((u32)task, magic), pr = task - seg * npr;
+        const int x = 2 * pr < rw - 2 ? 2 * pr : rw - 2, ya = seg * SEGR < rh - SEGR ? seg * SEGR : rh - SEGR;
+        rp_sums_col_task<S, SEGR, GS>(rowsum + ya * rw + x, rw, gs, ya * rw + x);
+    }
+}
+
+// wavefront-instructions of a pass: whole wavefronts of tasks x instructions per task (static counts of the task bodies)
+#ifdef SID_SUMS_BY_ROUNDS
+// (A/B builds: the longest chain of a thread instead - rounds of the workgroup x instructions per task)
+#define SID_SUMS_GROUPS(tasks) (((tasks) + kBlockM - 1) / kBlockM)
+#else
+#define SID_SUMS_GROUPS(tasks) (((tasks) + 63) >> 6)
+#endif
+__device__ __forceinline__ int rp_sums_row_cost(int wh, int rw, int seg) { return SID_SUMS_GROUPS(wh * ((rw + seg - 1) / seg)) * (5 * seg + 24); }
+__device__ __forceinline__ int rp_sums_col_cost(int rh, int rw, int s, int segr)
+{
+    return SID_SUMS_GROUPS(((rw + 1) >> 1) * ((rh + segr - 1) / segr)) * (2 * (s + segr - 1) + 2 * s + 6 * segr + 12);
+}
+
+template <int S, bool GS, bool BIG = false>
 __device__ __noinline__ void rp_sums(u32 *gsout)
 {
     SID_PHASE_LOCALS;
     u32 *gs = GS ? gsout : reinterpret_cast<u32 *>(smem + G.sii_off);
     const uint8_t *win = smem + G.win_off;
     u32 *rowsum = tab_ptr<BIG, u32>(G, smem, BIG ? G.ccm_off : G.u_off);   // (big layouts: where the NCC matrix will be)
-    const int s = G.s, wh = G.wh, rh = G.rh, rw = G.rw, wpitch = G.wpitch;
-    {   // along the rows: thread = (window row y, segment of placements)
-        int nseg = kBlockM / wh; nseg = nseg < 1 ? 1 : (nseg > rw ? rw : nseg);
-        const int per = (rw + nseg - 1) / nseg;
-        for (int task = tid; task < wh * nseg; task += kBlockM) {
-            const int y = task / nseg, seg = task - y * nseg;
-            const int xa = seg * per, xb = xa + per < rw ? xa + per : rw;
-            if (xa >= xb) continue;
-            const int8_t *row = reinterpret_cast<const int8_t *>(win) + y * wpitch + xa;
-            int c = 0;
-#pragma unroll 8
-            for (int j = 0; j < s; ++j) { const int v = row[j]; c += v * v; }
-            rowsum[y * rw + xa] = (u32)c;
-#pragma unroll 4
-            for (int x = 1; x < xb - xa; ++x) {
-                const int vo = row[x - 1], vn = row[x + s - 1];
-                c += vn * vn - vo * vo;
-                rowsum[y * rw + xa + x] = (u32)c;
-            }
-        }
+    // (wavefront-uniform: scalar registers, scalar branches)
+    const int wh = __builtin_amdgcn_readfirstlane(G.wh), rh = __builtin_amdgcn_readfirstlane(G.rh), rw = __builtin_amdgcn_readfirstlane(G.rw);
+    const int wpitch = __builtin_amdgcn_readfirstlane(G.wpitch);
+    {   // along the rows
+        int seg = 8, best = rp_sums_row_cost(wh, rw, 8);
+        for (int c = 16; c <= 32; c += 8) { const int v = rp_sums_row_cost(wh, rw, c); if (v < best) { best = v; seg = c; } }
+        if (seg == 8) rp_sums_rows<S, 8>(win, rowsum, wh, rw, wpitch);
+        else if (seg == 16) rp_sums_rows<S, 16>(win, rowsum, wh, rw, wpitch);
+        else if (seg == 24) rp_sums_rows<S, 24>(win, rowsum, wh, rw, wpitch);
+        else rp_sums_rows<S, 32>(win, rowsum, wh, rw, wpitch);
     }
     __syncthreads();
-    {   // down the columns: thread = (placement column x, segment of output rows)
-        int nseg = kBlockM / rw; nseg = nseg < 1 ? 1 : (nseg > rh ? rh : nseg);
-        const int per = (rh + nseg - 1) / nseg;
-        for (int task = tid; task < rw * nseg; task += kBlockM) {
-            const int seg = task / rw, x = task - seg * rw;
-            const int ya = seg * per, yb = ya + per < rh ? ya + per : rh;
-            if (ya >= yb) continue;
-            const u32 *col = rowsum + ya * rw + x;
-            u32 acc = 0;
-#pragma unroll 8
-            for (int i = 0; i < s; ++i) acc += col[i * rw];
-            sii_put(gs, ya * rw + x, acc);
-#pragma unroll 4
-            for (int y = 1; y < yb - ya; ++y) {
-                acc += col[(y + s - 1) * rw] - col[(y - 1) * rw];
-                sii_put(gs, (ya + y) * rw + x, acc);
-            }
-        }
+    {   // down the columns (rh >= 2: the kernel refuses windows below s + 1 rows)
+        int segr = 2, best = rp_sums_col_cost(rh, rw, S, 2);
+        for (int c = 4; c <= 16 && c <= rh; c += c) { const int v = rp_sums_col_cost(rh, rw, S, c); if (v < best) { best = v; segr = c; } }
+        if (segr == 2) rp_sums_cols<S, 2, GS>(rowsum, gs, rh, rw);
+        else if (segr == 4) rp_sums_cols<S, 4, GS>(rowsum, gs, rh, rw);
+        else if (segr == 8) rp_sums_cols<S, 8, GS>(rowsum, gs, rh, rw);
+        else rp_sums_cols<S, 16, GS>(rowsum, gs, rh, rw);
     }
     __syncthreads();                                                   // the row sums are dead; the stores are visible to the workgroup
 }
@@ -1653,8 +1741,9 @@ template <int S, int BAND = 4, int PAIRED = 0, int PITCH = 0, bool BIG = false>
 __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM) void pm_kernel_rp(const PMArgs A)
 {
     // (wave priorities: set inside the non-inlined phases - none in this body, see SID_SETPRIO_TS)
-    // (three wavefronts per point: 11 window + 5 patch dwords per thread cover what 10 + 4 do with four)
-    constexpr int kWin = rp_pitch_is_w3(PITCH) ? 11 : 10, kPat = rp_pitch_is_w3(PITCH) ? 5 : 4;
+    // (three wavefronts per point: 9 window dwords per thread - the pixel dwords of borders up to 23, the class's last - and 5
+    // patch dwords cover what 10 + 4 do with four)
+    constexpr int kWin = rp_pitch_is_w3(PITCH) ? 9 : 10, kPat = rp_pitch_is_w3(PITCH) ? 5 : 4;
     constexpr bool kPrio = PAIRED == 0 && ((SID_P_PRE) | (SID_P_SWEEP) | (SID_P_POST) | (SID_P_WIN) | (SID_P_HES)) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     MiscM *m = reinterpret_cast<MiscM *>(smem);
@@ -1746,7 +1835,7 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
         const int hist_off = BIG ? L.u_off + 2 * L.trow_bytes : L.ccm_off + round_up(rh * rw * 4, 16);
         G->hist_off = (K <= kAnglesPerGroup && !(GS && own_hes) && hist_off + 5120 <= L.total) ? hist_off : 0;
         G->pr0 = pr0; G->pc0 = pc0;
-        G->win_magic = 0xffffffffu / (u32)(L.wpitch >> 2) + 1u; G->patch_magic = 0xffffffffu / (u32)(L.ppitch >> 2) + 1u;
+        G->win_magic = 0xffffffffu / (u32)((ww + 3) >> 2) + 1u; G->patch_magic = 0xffffffffu / (u32)(L.ppitch >> 2) + 1u;
         G->rw_magic = 0xffffffffu / (u32)rw + 1u;
         G->r0 = r0; G->c0 = c0; G->c1 = c1; G->r1 = r1; G->nd = (double)(s * s);
         m->zero_flag = 0; m->gmax_key = 0x007fffffu /* f2key(-inf) */; m->qcount = 0; m->any_const = 0;
@@ -1774,7 +1863,7 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
     SID_STAMP(1);
     SID_STAMP(16);
 #ifndef SID_ABLATE_SUMS
-    rp_sums<GS, BIG>(gs);                                                   // ends with a barrier: the row sums are dead
+    rp_sums<S, GS, BIG>(gs);                                                   // ends with a barrier: the row sums are dead
 #endif
     SID_STAMP(2);
     if (!patch_early) ph_patch(A.img1, A.rows1, A.cols1, A.stride1);
