@@ -67,7 +67,11 @@ extern "C" {
                                      * Orders 2..5 are scipy's spline interpolation: the WHOLE image 1 goes through scipy's recursive
                                      * B-spline prefilter once per pair (float64 coefficients, 8 B per pixel x 2 buffers of device
                                      * memory, kept with the handle until the pair changes), then every template sample is the
-                                     * tensor product of n + 1 weights per axis - scipy's arithmetic operation for operation.      */
+                                     * tensor product of n + 1 weights per axis - scipy's arithmetic operation for operation.
+                                     * "The pair changes" = a call of sid_pm_upload_pair / sid_pm_select_pair / sid_pm_bind_pair: the
+                                     * coefficients, and the templates of the resident points sampled from them, are computed at the
+                                     * first run after such a call and KEPT.  Orders 0 and 1 read the pixels at every run.  Whoever
+                                     * overwrites a borrowed pair in place calls sid_pm_bind_pair again (see there).                */
 
 typedef struct sid_pm_ctx sid_pm_ctx;
 
@@ -126,7 +130,13 @@ int sid_pm_upload_pair(sid_pm_ctx *ctx, int slot,
                        const uint8_t *img2, int64_t rows2, int64_t cols2, int64_t stride2);
 int sid_pm_select_pair(sid_pm_ctx *ctx, int slot);
 
-/* Borrow images already in device memory (e.g. torch uint8 tensors). */
+/* Borrow images already in device memory (e.g. torch uint8 tensors).
+ * When the pixels are read: with rot_order 0 and 1 at every sid_pm_run, so a caller who overwrites the borrowed buffers in place
+ * (and orders that write before the run) gets the new pixels with no further call.  With rot_order 2..5 the spline coefficients
+ * of image 1, and the templates of the resident points sampled from them, are computed at the FIRST run after sid_pm_bind_pair /
+ * sid_pm_upload_pair / sid_pm_select_pair and kept: a later run would match the templates of the old image 1 against the new
+ * image 2.  A caller who changes the pixels in place must call sid_pm_bind_pair again - the same pointers will do; the call
+ * costs nothing but makes the next run compute the coefficients and templates anew. */
 int sid_pm_bind_pair(sid_pm_ctx *ctx,
                      const uint8_t *d_img1, int64_t rows1, int64_t cols1, int64_t stride1,
                      const uint8_t *d_img2, int64_t rows2, int64_t cols2, int64_t stride2);
@@ -239,7 +249,9 @@ int sid_pm_rotate_and_match(sid_pm_ctx *ctx, double c1, double r1, int img_size,
                             double out5[5], int32_t ij3[3], float *ccm, int64_t ccm_cap, uint8_t *best_template);
 
 /* get_template (pmlib.py:89-115): the s x s uint8 template around (c, r) of a host image, rot4 = {cos a, sin a, tcT0, tcT1}
- * as above; rot_order 0 or 1.  Only the part of the image the samples can touch travels to the device. */
+ * as above (every entry finite and below 1e6 in magnitude, as in `rot`: SID_PM_ERR_ARG otherwise, before any device call);
+ * rot_order 0..5.  Orders 0 and 1: only the part of the image the samples can touch travels to the device; orders 2..5: the
+ * whole image (scipy prefilters all of it). */
 int sid_pm_get_template(int device, const uint8_t *img, int64_t rows, int64_t cols, int64_t stride, double c, double r,
                         const double rot4[4], int img_size, int rot_order, uint8_t *out);
 

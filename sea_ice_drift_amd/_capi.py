@@ -330,6 +330,10 @@ class PMContext(object):
         self.device = int(device)
         self.n = 0
         self._keep = []
+        # (rows, cols) of image 2 per owned slot and of the borrowed binding, and which of them is current - the C handle's
+        # cur / cur_slot mirrored, for rotate_and_match(window=None)
+        self._shape2 = {}
+        self._cur = None
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h.value:
@@ -360,8 +364,16 @@ class PMContext(object):
         _check(lib().sid_pm_upload_pair(self._h, int(slot),
                                         _p(img1, _u8p), img1.shape[0], img1.shape[1], img1.strides[0],
                                         _p(img2, _u8p), img2.shape[0], img2.shape[1], img2.strides[0]))
+        self._uploaded(slot, img2)
         if select:
             self.select_pair(slot)
+
+    def _uploaded(self, slot, img2):
+        """Image 2 of ``slot`` has this shape now; the slot becomes current as in sid_pm_upload_pair: the first pair, a refresh
+        of the selected slot, or a borrowed binding was current."""
+        self._shape2[int(slot)] = (int(img2.shape[0]), int(img2.shape[1]))
+        if self._cur is None or self._cur == int(slot) or self._cur == 'bound':
+            self._cur = int(slot)
 
     def upload_pair_background(self, img1, img2, slot=0):
         """upload_pair on a worker thread, entered before this returns: the C call runs without the interpreter lock,
@@ -389,6 +401,7 @@ class PMContext(object):
         t = threading.Thread(target=run, daemon=True)
         t.start()
         entered.wait()
+        self._uploaded(s, img2)
         ctx = self
 
         class _Pending:
@@ -404,13 +417,21 @@ class PMContext(object):
 
     def select_pair(self, slot):
         _check(lib().sid_pm_select_pair(self._h, int(slot)))
+        self._cur = int(slot)
 
     def bind_pair_ptr(self, p1, rows1, cols1, stride1, p2, rows2, cols2, stride2):
         _check(lib().sid_pm_bind_pair(self._h, C.c_void_p(int(p1)), rows1, cols1, stride1,
                                       C.c_void_p(int(p2)), rows2, cols2, stride2))
+        self._shape2['bound'] = (int(rows2), int(cols2))
+        self._cur = 'bound'
 
     def bind_pair_tensors(self, t1, t2):
-        """Borrow two CUDA/HIP uint8 torch tensors (2-D, unit inner stride)."""
+        """Borrow two CUDA/HIP uint8 torch tensors (2-D, unit inner stride); they stay borrowed until the next bind / upload /
+        select.  When their pixels are read: with rot_order 0 and 1 at every ``run()``, so tensors overwritten in place (on the
+        handle's stream, or synchronised) are matched with their new content.  With rot_order 2..5 the spline coefficients of
+        image 1 and the templates of the resident points sampled from them are computed at the first ``run()`` after the bind and
+        kept: after changing the pixels in place call ``bind_pair_tensors`` again - with the same tensors - or the next run
+        matches the templates of the old image 1 (include/sid_pm.h sid_pm_bind_pair)."""
         for t in (t1, t2):
             if t.dim() != 2 or t.stride(1) != 1 or str(t.dtype) != 'torch.uint8' or not t.is_cuda:
                 raise TypeError('need 2-D uint8 device tensors with unit inner stride')
@@ -506,13 +527,15 @@ class PMContext(object):
     def rotate_and_match(self, c1, r1, img_size, alpha0, angles, rot=None, flags=HES_NORM, window=None, want_ccm=True,
                          want_template=True):
         """``sid_pm_rotate_and_match`` on the handle's current pair: the templates around (c1, r1) of image 1 against ``window`` =
-        (row0, col0, rows, cols) of image 2 (None: the whole image).  -> dict(out = dc, dr, a, r, h; ij = peak row, peak column,
+        (row0, col0, rows, cols) of image 2 (None: the whole of image 2 of the current pair).  -> dict(out = dc, dr, a, r, h; ij = peak row, peak column,
         angle index (-1: NaN point); ccm [rh, rw] float32 and template [s, s] uint8, None for a NaN point)."""
         angles = _f64(angles)
         rot = _rot_arg(rot, angles, alpha0, img_size)
         s = int(img_size)
         if window is None:
-            raise ValueError('window = (row0, col0, rows, cols) of image 2')
+            if self._cur is None:
+                raise ValueError('rotate_and_match needs an image pair (upload_pair / bind_pair first)')
+            window = (0, 0) + self._shape2[self._cur]
         r0, c0, wh, ww = [int(v) for v in window]
         rh, rw = wh - s + 1, ww - s + 1
         out5 = np.zeros(5, dtype=np.float64)
@@ -547,7 +570,8 @@ class PMContext(object):
 
 
 def get_template(img, c, r, rot4, img_size, rot_order=0, device=0):
-    """``sid_pm_get_template``: the s x s uint8 template around (c, r) of a host uint8 image (pmlib.py:89-115)."""
+    """``sid_pm_get_template``: the s x s uint8 template around (c, r) of a host uint8 image (pmlib.py:89-115), ``rot_order``
+    0..5; ``rot4`` = (cos a, sin a, tcT0, tcT1), every entry finite and below 1e6 in magnitude (SidPmError -1 otherwise)."""
     img = _u8(img)
     rot4 = _f64(rot4).reshape(4)
     s = int(img_size)

@@ -1330,6 +1330,8 @@ SID_EXPORT int sid_pm_get_template(int device, const uint8_t *img, int64_t rows,
     if (img_size < 1 || img_size > 4096) return fail(SID_PM_ERR_UNSUPPORTED, "img_size=%d", img_size);
     if (rot_order < 0 || rot_order > 5) return fail(SID_PM_ERR_UNSUPPORTED, "rot_order=%d: scipy's spline orders are 0..5", rot_order);
     if (!(fabs(c) < 1e15 && fabs(r) < 1e15)) return fail(SID_PM_ERR_ARG, "non-finite centre");
+    // (make_rot's rule, before any device call: `reach` below goes through floor() and a cast)
+    for (int k = 0; k < 4; ++k) if (!(fabs(rot4[k]) < 1e6)) return fail(SID_PM_ERR_ARG, "rot4 holds a non-finite or absurd value");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SID_PM_ERR_NODEVICE, "no such device");
     Guard g(device);

@@ -480,7 +480,7 @@ def pm_dispatch(img1, img2, c1, r1, c2fg, r2fg, border, img_size, alpha0, device
 
 def get_template(img, c, r, a, s, rot_order=0, **kwargs):
     """Rotated and shifted square template: same signature and return as the reference's get_template (pmlib.py:89-115) -
-    the (s, s) uint8 array scipy's affine_transform would give for ``rot_order`` 0 or 1, sampled on the GPU."""
+    the (s, s) uint8 array scipy's affine_transform would give for ``rot_order`` 0..5, sampled on the GPU."""
     if isinstance(rot_order, bool) or rot_order not in (0, 1, 2, 3, 4, 5):
         raise RuntimeError('rot_order=%r: spline order not supported (scipy.ndimage.affine_transform takes 0..5)' % (rot_order,))
     return _capi.get_template(img, c, r, rotation_terms(a, s), s, rot_order=int(rot_order), device=int(kwargs.get('device', 0)))

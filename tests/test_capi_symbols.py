@@ -4,6 +4,9 @@ import ctypes
 import os
 import re
 
+import numpy as np
+import pytest
+
 from sea_ice_drift_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,6 +72,24 @@ def test_argument_errors_without_a_device():
     assert lib.sid_pm_create(0, None) == -1
     assert lib.sid_pm_run(None) == -1
     assert b'null ctx' in lib.sid_pm_last_error()
+
+
+def test_get_template_rejects_a_non_finite_rot4_before_any_device_call():
+    """rot4 feeds floor() and a cast on the host (the part of the image that travels): every entry must satisfy make_rot's rule,
+    fabs(v) < 1e6, or the call is SID_PM_ERR_ARG - on a machine without a device too, so the check precedes every device call."""
+    img = np.full((8, 8), 9, dtype=np.uint8)
+    for order in (0, 3):
+        for bad in (np.nan, np.inf, -np.inf, 1e6, -1e300):
+            for k in range(4):
+                rot4 = np.array([1.0, 0.0, 3.0, 3.0])
+                rot4[k] = bad
+                with pytest.raises(_capi.SidPmError) as e:
+                    _capi.get_template(img, 4.0, 4.0, rot4, 4, rot_order=order)
+                assert e.value.code == -1 and 'rot4' in str(e.value), (order, bad, k)
+    try:                                                              # (an ordinary rot4 passes the check: no device here, or a template)
+        assert _capi.get_template(img, 4.0, 4.0, [1.0, 0.0, 3.0, 3.0], 4).shape == (4, 4)
+    except _capi.SidPmError as e:
+        assert e.code == -5
 
 
 def test_matcher_argument_errors_without_a_device():
