@@ -142,9 +142,16 @@ __host__ __device__ inline MfmaLdsLayout mfma_lds_layout(int wh, int ww, int s, 
     L.pradius = r + 1;
     L.pdim = 2 * L.pradius + 2;
     L.ppitch = round_up(L.pdim, 4);
-    L.patch_off = L.u_off + round_up(L.tab_rows * L.arow + 16, 16);   // + 16 scratch bytes
-    L.queue_off = round_up(L.patch_off + L.pdim * L.ppitch + 1, 16);  // + one byte = 128 behind the patch (flagged table entries)
     L.trow_bytes = 4 * (s + kTrowPad) * 16;
+    // ph_hessian lays 5 KB of median scratch (4 KB of histograms + kMedList keys) over the two dead operand blocks, in front
+    // of the NCC matrix: sides 2 and 3, whose blocks are 2432 / 2496 bytes, take the slack of a side-4 block
+    if (L.trow_bytes < 2560) L.trow_bytes = 2560;
+    // the winner's two operand blocks are staged over the dead sweep table FROM the patch, so the patch lies behind them as
+    // well: up to side 5 (paired: 4) the table is the shorter of the two
+    int tab = round_up(L.tab_rows * L.arow + 16, 16);                 // + 16 scratch bytes
+    if (tab < 2 * L.trow_bytes) tab = 2 * L.trow_bytes;
+    L.patch_off = L.u_off + tab;
+    L.queue_off = round_up(L.patch_off + L.pdim * L.ppitch + 1, 16);  // + one byte = 128 behind the patch (flagged table entries)
     int u = rh * ww * 4;                                          // column sums
     const int sweep = L.queue_off + kQueueCap * 16 - L.u_off;
     if (u < sweep) u = sweep;

@@ -99,7 +99,7 @@ struct Geo {
     int gpitch, arow0, tab_rows, ones_slot;   // operand-table geometry (mfma_lds_layout) and the all-ones slot: 15, or 7 paired
     int win_off, sii_off, u_off, patch_off, ppitch, pdim, pradius, queue_off, trow_bytes;
     int pr0, pc0;                    // patch origin on image 1
-    u32 win_magic;                   // floor(2^32 / dwr) + 1, dwr = (ww + 3) / 4 the pixel dwords of a window row: idx / dwr == umulhi(idx, win_magic) for idx < 2^16
+    u32 win_magic;                   // floor(2^32 / dwr) + 1, dwr = (ww + 3) / 4 the pixel dwords of a window row: idx / dwr == umulhi(idx, win_magic) for idx < 2^16 and dwr > 1
     u32 patch_magic, rw_magic;       // same for ppitch/4 and for rw
     int band;                        // output rows per sweep work item (kernel template parameter)
     int wp_off, wp_pitch, wp_rows, strip_off, wrows, npair, nsingle;   // row-pair kernel (RpLdsLayout)
@@ -534,7 +534,7 @@ __device__ __noinline__ void ph_window_t(const uint8_t *img2, long long rows2, l
             if (base + u * kBlockM < ndw) {
                 const int idx = base + u * kBlockM + tid;
                 const int idc = idx < ndw ? idx : 0;
-                const int row = (int)__umulhi((u32)idc, magic);
+                const int row = dwr > 1 ? (int)__umulhi((u32)idc, magic) : idc;   // (one dword per row - a window of at most 4 columns, side 2 at border 0 -: 2^32 / 1 + 1 is no 32-bit magic)
                 const int dq = idc - row * dwr;
                 dstv[u] = row * dw_per_row + dq;
                 mskv[u] = dq == dwr - 1 ? tailmask : 0xffffffffu;      // (every task holds a pixel; the last of a row ww & 3 of them)
@@ -1455,7 +1455,7 @@ __device__ __noinline__ void ph_hessian(unsigned flags, int iy, int ix, float be
     float *hes = tab_ptr<BIG, float>(G, smem, G.hes_off);
     const float *ccm = tab_ptr<BIG, float>(G, smem, G.ccm_off);
     u32 *hist4 = reinterpret_cast<u32 *>(smem + G.u_off);             // winner operands are dead: 4 KB of histograms
-    u32 *medlist = hist4 + 1024;                                       // + 1 KB of keys (2 * trow_bytes >= 5 KB for every s)
+    u32 *medlist = hist4 + 1024;                                       // + 1 KB of keys (2 * trow_bytes >= 5 KB for every s: mfma_lds_layout)
     const int rh = G.rh, rw = G.rw, npos = G.npos;
     float rr = best_r;
     if (flags & 4u) {                                                  // mcc_norm (pmlib.py:171-172): on the unsmoothed matrix
@@ -1535,7 +1535,7 @@ __device__ __noinline__ void ph_hessian(unsigned flags, int iy, int ix, float be
                 for (int u = 0; u < kHes; ++u) {
                     const int q = base + u * kBlockM + tid;
                     const int qc = q < nin ? q : 0;
-                    const int yy = (int)__umulhi((u32)qc, imagic), xx = qc - yy * iw;
+                    const int yy = iw > 1 ? (int)__umulhi((u32)qc, imagic) : qc, xx = qc - yy * iw;   // (an interior one column wide: 2^32 / 1 + 1 is no 32-bit magic)
                     const float *f = ccm + (yy + 2) * rw + (xx + 2);
                     const float c = f[0], xr = f[2], xl = f[-2], yd = f[2 * rw], yu = f[-2 * rw];
                     d2xv[u] = ((xr - c) * 0.5f - (c - xl) * 0.5f) * 0.5f;
@@ -1544,7 +1544,7 @@ __device__ __noinline__ void ph_hessian(unsigned flags, int iy, int ix, float be
 #pragma unroll
                 for (int u = 0; u < kHes; ++u) {
                     const int q = base + u * kBlockM + tid;
-                    if (q < nin) { const int yy = (int)__umulhi((u32)q, imagic), xx = q - yy * iw; emit((yy + 2) * rw + xx + 2, d2xv[u], d2yv[u]); }
+                    if (q < nin) { const int yy = iw > 1 ? (int)__umulhi((u32)q, imagic) : q, xx = q - yy * iw; emit((yy + 2) * rw + xx + 2, d2xv[u], d2yv[u]); }
                 }
             }
         }

@@ -288,7 +288,7 @@ __device__ __forceinline__ void rp_sums_cols(const u32 *rowsum, u32 *gs, int rh,
     const int npr = (rw + 1) >> 1, nseg = (rh + SEGR - 1) / SEGR, ntask = npr * nseg;
     const u32 magic = 0xffffffffu / (u32)npr + 1u;
     for (int task = tid; task < ntask; task += kBlockM) {
-        const int seg = (int)__umulhi((u32)task, magic), pr = task - seg * npr;
+        const int seg = npr > 1 ? (int)__umulhi((u32)task, magic) : task, pr = task - seg * npr;   // (one column pair - a matrix two wide -: 2^32 / 1 + 1 is no 32-bit magic)
         const int x = 2 * pr < rw - 2 ? 2 * pr : rw - 2, ya = seg * SEGR < rh - SEGR ? seg * SEGR : rh - SEGR;
         rp_sums_col_task<S, SEGR, GS>(rowsum + ya * rw + x, rw, gs, ya * rw + x);
     }
