@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SID_PM_ABI_VERSION 5
+#define SID_PM_ABI_VERSION 6
 
 /* return codes */
 #define SID_PM_OK               0
@@ -72,6 +72,24 @@ extern "C" {
                                      * coefficients, and the templates of the resident points sampled from them, are computed at the
                                      * first run after such a call and KEPT.  Orders 0 and 1 read the pixels at every run.  Whoever
                                      * overwrites a borrowed pair in place calls sid_pm_bind_pair again (see there).                */
+
+#define SID_PM_SUBPIXEL 128u        /* NOT the reference's (ABI 6): sub-pixel peak.  Bit 7; bit 6 (64) stays an unknown flag.  c2, r2 (dc, dr of
+                                     * sid_pm_rotate_and_match) get the offset of the vertex of the parabola through the peak of the
+                                     * winning angle's NCC matrix and its two neighbours along each axis.  R = best_result, rh x rw
+                                     * float32, the RAW matrix (before hes_smth smooths it, untouched by mcc_norm), (iy, ix) = out_ij:
+                                     *     fit(a, b, c):            a, b, c converted float32 -> float64
+                                     *         x = a - b ; y = c - b ; den = x + y ; num = a - c
+                                     *         if den == 0.0: return 0.0
+                                     *         d = (num / den) * 0.5 ;  return min(max(d, -0.5), 0.5)
+                                     *     dx = fit(R[iy][ix-1], R[iy][ix], R[iy][ix+1])  if 0 < ix < rw-1  else 0.0
+                                     *     dy = fit(R[iy-1][ix], R[iy][ix], R[iy+1][ix])  if 0 < iy < rh-1  else 0.0
+                                     *     out[0] = c2 + dx ;  out[1] = r2 + dy
+                                     * Every operation is one IEEE double rounding (no fused multiply-add, correctly rounded division);
+                                     * c2, r2 are computed exactly as without the flag and the offset is one more double addition,
+                                     * applied last.  Angle, r, h, out_ij, best_result, best_template and NaN points do not change.
+                                     * A peak is the FIRST maximum in row-major order, so a < b strictly and den < 0: the den == 0
+                                     * branch is a guard; c == b gives exactly +0.5.  sid_pm_get_hessian refuses the flag; the
+                                     * sid_pm_estimate_* functions take it and estimate the same cost.                              */
 
 typedef struct sid_pm_ctx sid_pm_ctx;
 

@@ -15,8 +15,9 @@ HES_NORM = 1
 HES_SMTH = 2
 MCC_NORM = 4
 ROT_ORDER1 = 8          # rot_order=1: bilinear template sampling (include/sid_pm.h)
+SUBPIXEL = 128          # subpixel=True: parabolic sub-pixel peak (SID_PM_SUBPIXEL; not the reference's)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # every symbol include/sid_pm.h declares
 SYMBOLS = (
@@ -298,10 +299,11 @@ def rot_order_flag(order):
     return (int(order) & 7) << 3
 
 
-def flags_from_kwargs(hes_norm=True, hes_smth=False, mcc_norm=False, rot_order=0):
+def flags_from_kwargs(hes_norm=True, hes_smth=False, mcc_norm=False, rot_order=0, subpixel=False):
     if isinstance(rot_order, bool) or rot_order not in (0, 1, 2, 3, 4, 5):
         raise ValueError('rot_order=%r: spline orders 0..5 (scipy.ndimage.affine_transform)' % (rot_order,))
-    return ((HES_NORM if hes_norm else 0) | (HES_SMTH if hes_smth else 0) | (MCC_NORM if mcc_norm else 0) | rot_order_flag(rot_order))
+    return ((HES_NORM if hes_norm else 0) | (HES_SMTH if hes_smth else 0) | (MCC_NORM if mcc_norm else 0) | rot_order_flag(rot_order)
+            | (SUBPIXEL if subpixel else 0))
 
 
 def pm_batch(img1, img2, c1, r1, c2fg, r2fg, border, img_size, alpha0, angles, rot=None, flags=HES_NORM):

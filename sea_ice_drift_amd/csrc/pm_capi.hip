@@ -22,6 +22,8 @@
 #include "pm_kernel.h"
 #include "pm_large.h"
 
+static_assert(SID_PM_SUBPIXEL == sid::kSubpixel, "the kernels test the bit of include/sid_pm.h");
+
 #define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
@@ -368,7 +370,7 @@ int check_sweep(int img_size, const double *angles, int n_angles, uint32_t flags
     if (n_angles > sid::kMaxAngles) return fail(SID_PM_ERR_UNSUPPORTED, "more than %d angles", sid::kMaxAngles);
     if (img_size < 2 || img_size > sid::kLargeMaxSide)
         return fail(SID_PM_ERR_UNSUPPORTED, "img_size=%d: the kernels support 2..%d", img_size, sid::kLargeMaxSide);
-    if (flags & ~(SID_PM_HES_NORM | SID_PM_HES_SMTH | SID_PM_MCC_NORM | SID_PM_ROT_ORDER(7))) return fail(SID_PM_ERR_ARG, "unknown flag bits");
+    if (flags & ~(SID_PM_HES_NORM | SID_PM_HES_SMTH | SID_PM_MCC_NORM | SID_PM_ROT_ORDER(7) | SID_PM_SUBPIXEL)) return fail(SID_PM_ERR_ARG, "unknown flag bits");
     if (((flags >> 3) & 7u) > 5u) return fail(SID_PM_ERR_UNSUPPORTED, "rot_order %u: scipy's spline orders are 0..5", (flags >> 3) & 7u);
     return SID_PM_OK;
 }

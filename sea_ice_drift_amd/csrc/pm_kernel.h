@@ -1,10 +1,12 @@
 // Shared between the HIP kernel (pm_kernel_mfma.hip) and the host C-ABI (pm_capi.hip).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace sid {
 
 constexpr int kMaxAngles = 64;
+constexpr uint32_t kSubpixel = 128u;    // SID_PM_SUBPIXEL (include/sid_pm.h), bit 7 of PMArgs::flags / LwParams::flags
 
 // Row-pair kernel: everything a workgroup needs to know about its point in ONE record per launch position - the point's index,
 // the offset of its sum w'^2 block (PMArgs::gsii, units of 64 entries) and its five input values - so that the prologue
@@ -86,6 +88,27 @@ struct PMArgs {
 };
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// SID_PM_SUBPIXEL (include/sid_pm.h): offset of the vertex of the parabola through three neighbouring float32 NCC values - a, c the
+// neighbours of the peak b along one axis - in IEEE double, one rounding per operation (the build has no fused multiply-add;
+// the division is the correctly rounded one).  At an interior first-maximum peak a < b strictly (the left / upper neighbour
+// precedes the peak in row-major order) and c <= b, so den < 0: the den == 0 branch is a guard no arg-max peak reaches.  c == b
+// gives exactly +0.5; the clamp only catches an overshoot in the last bit.
+__host__ __device__ inline double subpixel_fit(float fa, float fb, float fc)
+{
+    const double a = (double)fa, b = (double)fb, c = (double)fc;
+    const double x = a - b, y = c - b, den = x + y, num = a - c;
+    if (den == 0.0) return 0.0;
+    const double d = (num / den) * 0.5;
+    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
+}
+// dx, dy of the peak (iy, ix) of the raw rh x rw NCC matrix R; 0 along an axis on whose first or last line the peak lies
+__host__ __device__ inline void subpixel_offsets(const float *R, int rh, int rw, int iy, int ix, double &dx, double &dy)
+{
+    const float *p = R + (size_t)iy * (size_t)rw + ix;
+    dx = (ix > 0 && ix < rw - 1) ? subpixel_fit(p[-1], p[0], p[1]) : 0.0;
+    dy = (iy > 0 && iy < rh - 1) ? subpixel_fit(p[-rw], p[0], p[rw]) : 0.0;
+}
 
 // ---- MFMA kernel (pm_kernel_mfma.hip) ----
 constexpr int kMiscMfmaBytes = 2688;

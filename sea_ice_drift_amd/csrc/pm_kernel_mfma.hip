@@ -90,6 +90,7 @@ struct MiscM {                       // LDS offset 0, kMiscMfmaBytes reserved
     __attribute__((aligned(16))) float biasf[kSlots];   // 0, or -inf for a dead slot
     float maxA;
     int any_const;
+    double sub[2];                   // SID_PM_SUBPIXEL: dx, dy of the peak, from the raw NCC matrix of the winning angle (ph_subpixel)
 };
 
 // Per-point geometry, written once by thread 0 and read by every phase (the phases are separate
@@ -1443,6 +1444,24 @@ __device__ __noinline__ void ph_winner(int ka, long long *dbg_cycles)
 }
 
 // ---------------------------------------------------------------------------------------------
+// SID_PM_SUBPIXEL: the parabolic offsets of the peak (subpixel_fit, pm_kernel.h) from the winner's NCC matrix wherever it lives
+// (LDS - the kept-accumulator winner leaves it there like the others - or the point's block of global memory: tab_ptr<BIG>),
+// left in m->sub[0..1] for the thread that writes the result row.  First thing in ph_hessian and ph_hessian_fast: every form of
+// the winner's matrix ends with a barrier, and ph_hessian smooths the matrix IN PLACE under hes_smth (behind a barrier of its
+// own) - the offsets are those of the RAW matrix.  Five loads and two double divisions by one thread; nothing else of MiscM
+// that the Hessian code touches lies near m->sub.
+// ---------------------------------------------------------------------------------------------
+template <bool BIG = false>
+__device__ __forceinline__ void ph_subpixel(int iy, int ix)
+{
+    SID_PHASE_LOCALS;
+    if (tid != 0) return;
+    double dx, dy;
+    subpixel_offsets(tab_ptr<BIG, float>(G, smem, G.ccm_off), G.rh, G.rw, iy, ix, dx, dy);
+    m->sub[0] = dx; m->sub[1] = dy;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Phase 5: Hessian at the peak (pmlib.py:36-59, :167) and the optional MCC normalisation.
 // hes aliases sii.  Returns h, r in m->red_f[0..1].
 // ---------------------------------------------------------------------------------------------
@@ -1456,6 +1475,7 @@ __device__ __noinline__ void ph_hessian(unsigned flags, int iy, int ix, float be
     const float *ccm = tab_ptr<BIG, float>(G, smem, G.ccm_off);
     u32 *hist4 = reinterpret_cast<u32 *>(smem + G.u_off);             // winner operands are dead: 4 KB of histograms
     u32 *medlist = hist4 + 1024;                                       // + 1 KB of keys (2 * trow_bytes >= 5 KB for every s: mfma_lds_layout)
+    if (flags & kSubpixel) ph_subpixel<BIG>(iy, ix);
     const int rh = G.rh, rw = G.rw, npos = G.npos;
     float rr = best_r;
     if (flags & 4u) {                                                  // mcc_norm (pmlib.py:171-172): on the unsmoothed matrix
@@ -1681,6 +1701,7 @@ __device__ __noinline__ void ph_hessian_fast(unsigned flags, int iy, int ix, flo
     const float *ccm = tab_ptr<BIG, float>(G, smem, G.ccm_off);
     u32 *hist = reinterpret_cast<u32 *>(smem + G.hist_off);            // 2048 16-bit counters, zero on entry; m->sel_cle = 0
     u32 *list = hist + 1024;                                           // kMedList keys
+    if (flags & kSubpixel) ph_subpixel<BIG>(iy, ix);
     const int rh = G.rh, rw = G.rw, npos = G.npos;
     const bool norm = (flags & 1u) != 0;
     double sx = 0.0, sxx = 0.0;
@@ -1988,8 +2009,11 @@ __global__ __launch_bounds__(BAND == 8 ? 512 : kMaxBlockM, BAND == 8 ? 2 : kOccM
 #endif
     SID_STAMP(7);
     if (tid == 0) {
-        out[0] = c2fg + ((double)ix - (double)(ww - s) / 2.0);
-        out[1] = r2fg + ((double)iy - (double)(wh - s) / 2.0);
+        double c2 = c2fg + ((double)ix - (double)(ww - s) / 2.0);
+        double r2 = r2fg + ((double)iy - (double)(wh - s) / 2.0);
+        if (A.flags & kSubpixel) { c2 += m->sub[0]; r2 += m->sub[1]; }
+        out[0] = c2;
+        out[1] = r2;
         out[2] = A.angles[ka];
         out[3] = (double)m->red_f[1];
         out[4] = (double)m->red_f[0];

@@ -1948,8 +1948,11 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
         const double c2fg_e = *reinterpret_cast<const volatile double *>(A.c2fg + pt);
         const double r2fg_e = *reinterpret_cast<const volatile double *>(A.r2fg + pt);
         const int ww_e = G->ww, wh_e = G->wh;
-        out[0] = c2fg_e + ((double)ix - (double)(ww_e - s) / 2.0);
-        out[1] = r2fg_e + ((double)iy - (double)(wh_e - s) / 2.0);
+        double c2 = c2fg_e + ((double)ix - (double)(ww_e - s) / 2.0);
+        double r2 = r2fg_e + ((double)iy - (double)(wh_e - s) / 2.0);
+        if (A.flags & kSubpixel) { c2 += m->sub[0]; r2 += m->sub[1]; }
+        out[0] = c2;
+        out[1] = r2;
         out[2] = A.angles[ka];
         out[3] = (double)m->red_f[1];
         out[4] = (double)m->red_f[0];

@@ -654,7 +654,13 @@ __global__ void lw_finish_kernel(const LwParams *Pv)
     float r = S->best_r;
     if (P.flags & 4u) { float med, sd; lw_med_std(S, 1, n, med, sd); r = (r - med) / sd; }
     const double dr = (double)S->iy - (double)(P.wh - P.s) / 2., dc = (double)S->ix - (double)(P.ww - P.s) / 2.;   // pmlib.py:168-169
-    P.out5[0] = P.add_c + dc; P.out5[1] = P.add_r + dr; P.out5[2] = P.angles[S->kbest];
+    double c2 = P.add_c + dc, r2 = P.add_r + dr;
+    if (P.flags & kSubpixel) {                                        // the raw matrix: hes_smth smooths into buffers of its own here
+        double dx, dy;
+        subpixel_offsets(lw_matrix(P, M_NCC), P.rh, P.rw, S->iy, S->ix, dx, dy);
+        c2 += dx; r2 += dy;
+    }
+    P.out5[0] = c2; P.out5[1] = r2; P.out5[2] = P.angles[S->kbest];
     P.out5[3] = (double)r; P.out5[4] = (double)h;
     if (P.ij3) { P.ij3[0] = S->iy; P.ij3[1] = S->ix; P.ij3[2] = S->kbest; }
 }

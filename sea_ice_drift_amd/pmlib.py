@@ -206,7 +206,8 @@ def _sweep_options(kwargs):
         raise RuntimeError('rot_order=%r: spline order not supported (scipy.ndimage.affine_transform takes 0..5)' % (rot_order,))
     angles = list(kwargs.get('angles', [-3, 0, 3]))
     flags = _capi.flags_from_kwargs(hes_norm=kwargs.get('hes_norm', True), hes_smth=kwargs.get('hes_smth', False),
-                                    mcc_norm=kwargs.get('mcc_norm', False), rot_order=int(rot_order))
+                                    mcc_norm=kwargs.get('mcc_norm', False), rot_order=int(rot_order),
+                                    subpixel=bool(kwargs.get('subpixel', False)))
     return angles, flags
 
 
@@ -450,7 +451,15 @@ def pm_dispatch(img1, img2, c1, r1, c2fg, r2fg, border, img_size, alpha0, device
     (``resolve_devices``): with more than one handle the points are sharded over them (``plan_shards``) and the rows
     merged back; the result equals the one-handle call's bit for bit.  ``img1`` = None then means that an earlier call
     with the same ``devices`` left the pair resident on these handles.  Not together with ``context``.
-    ``timings``: a dict that a call on several handles fills with the seconds of its stages (``_dispatch_sharded``)."""
+    ``timings``: a dict that a call on several handles fills with the seconds of its stages (``_dispatch_sharded``).
+
+    Keyword arguments that are NOT the reference's:
+
+    ``subpixel`` = False (default) | True - sub-pixel peak (include/sid_pm.h SID_PM_SUBPIXEL): ``c2``, ``r2`` get the offset of the
+        vertex of the parabola through the peak of the winning angle's raw cross-correlation matrix and its two neighbours
+        along each axis, within [-0.5, 0.5], 0 along an axis on whose first or last line the peak lies.  Nothing else
+        changes - angle, r, h and NaN points are those of ``subpixel=False`` bit for bit.  The consumer is ``libdefor``:
+        deformation from drift quantised to whole pixels is mostly staircase noise."""
     angles, flags = _sweep_options(kwargs)
     rot = rotation_table(angles, alpha0, img_size)
     if devices is not None:
@@ -525,7 +534,15 @@ def rotate_and_match(img1, c1, r1, img_size, image2, alpha0, angles=[-3, 0, 3], 
     seven NaNs when a rotated template touches a 0 pixel (pmlib.py:152-154).  ``image2`` is the search window - any rectangular
     uint8 array, up to a whole image (tests.py:336-337); its placements are tiled over the whole GPU (csrc/pm_large.hip).
     ``kwargs``: ``rot_order`` (0 / 1), ``hes_norm``, ``hes_smth`` as in the reference; ``device`` / ``context`` as in pm_dispatch.
-    A window with fewer than two placements along an axis raises ValueError (np.gradient does, in the reference)."""
+    A window with fewer than two placements along an axis raises ValueError (np.gradient does, in the reference).
+
+    Keyword arguments that are NOT the reference's:
+
+    ``subpixel`` = False (default) | True - sub-pixel peak (include/sid_pm.h SID_PM_SUBPIXEL): ``dc``, ``dr`` get the offset of the
+        vertex of the parabola through the peak of the winning angle's raw cross-correlation matrix and its two neighbours
+        along each axis, within [-0.5, 0.5], 0 along an axis on whose first or last line the peak lies.  Nothing else
+        changes - angle, r, h and NaN points are those of ``subpixel=False`` bit for bit.  The consumer is ``libdefor``:
+        deformation from drift quantised to whole pixels is mostly staircase noise."""
     kw = dict(kwargs, angles=angles, mtype=mtype, template_matcher=template_matcher, mcc_norm=mcc_norm)
     context = kw.pop('context', None)
     device = kw.pop('device', 0)
@@ -552,7 +569,10 @@ def rotate_and_match(img1, c1, r1, img_size, image2, alpha0, angles=[-3, 0, 3], 
 
 
 def use_mcc(c1, r1, c2fg, r2fg, border, img1, img2, img_size, alpha0, **kwargs):
-    """One point, same signature and return as the reference's use_mcc (pmlib.py:176-212)."""
+    """One point, same signature and return as the reference's use_mcc (pmlib.py:176-212).
+
+    Keyword arguments that are NOT the reference's: ``device`` / ``context`` / ``devices`` and ``subpixel`` as in ``pm_dispatch``
+    (``subpixel=True``: ``c2``, ``r2`` carry the parabolic sub-pixel offset of the peak)."""
     out = pm_dispatch(img1, img2, [c1], [r1], [c2fg], [r2fg], [border], img_size, alpha0, **kwargs)
     c2, r2, a, r, h = out[0]
     return c2, r2, a, np.float32(r), np.float32(h)
@@ -582,7 +602,12 @@ def pattern_matching(lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2,
         ``[0, 1, 2, 3]`` (``resolve_devices``).  With several handles the pair is uploaded to each of them while the host
         works on the first guess (evaluated on the first entry), the valid grid points are cut into one shard of equal
         estimated run time per handle (``plan_shards``) and every handle runs its shard; the seven grids equal those of the
-        one-handle call bit for bit.  ``threads``, the reference's parallelism argument, stays accepted and ignored."""
+        one-handle call bit for bit.  ``threads``, the reference's parallelism argument, stays accepted and ignored.
+    ``subpixel`` = False (default) | True - sub-pixel peak (include/sid_pm.h SID_PM_SUBPIXEL): the matched positions ``c2``, ``r2`` (hence ``u``, ``v``, ``lon2_dst``, ``lat2_dst``) get the offset of the
+        vertex of the parabola through the peak of the winning angle's raw cross-correlation matrix and its two neighbours
+        along each axis, within [-0.5, 0.5], 0 along an axis on whose first or last line the peak lies.  Nothing else
+        changes - angle, r, h and NaN points are those of ``subpixel=False`` bit for bit.  The consumer is ``libdefor``:
+        deformation from drift quantised to whole pixels is mostly staircase noise."""
     t0 = time.time()
     img1, img2 = n1[1], n2[1]
     _sweep_options(kwargs)                                            # unsupported options fail before any work

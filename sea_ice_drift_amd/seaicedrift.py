@@ -64,7 +64,10 @@ class SeaIceDrift(object):
     def get_drift_PM(self, lons, lats, lon1, lat1, lon2, lat2, **kwargs):
         """Same arguments and returns as the reference (seaicedrift.py:62-88):
         u, v, a, r, h, lon2_dst, lat2_dst on the (lons, lats) grid.  ``devices=`` (or the constructor's) spreads the grid
-        points over several GPUs (``pmlib.pattern_matching``)."""
+        points over several GPUs (``pmlib.pattern_matching``).
+
+        Keyword arguments that are NOT the reference's: those of ``pmlib.pattern_matching``, among them ``subpixel=True`` -
+        drift with the parabolic sub-pixel offset of the correlation peak, what ``libdefor`` wants to be fed."""
         if self.devices is not None:
             kwargs.setdefault('devices', self.devices)
         x1, y1 = self.n1.transform_points(lon1, lat1, 1)
