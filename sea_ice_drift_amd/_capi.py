@@ -46,6 +46,11 @@ FG_SYMBOLS = ('sid_fg_interp_linear', 'sid_fg_nearest_dist', 'sid_fg_distance_im
 DEFOR_SYMBOLS = ('sid_defor_triangulation', 'sid_defor_elems', 'sid_defor_triangulation_device', 'sid_defor_elems_device',
                  'sid_defor_debug_hypot', 'sid_defor_last_error', 'sid_defor_release')
 DEFOR_ERR_INDEX = -32   # include/sid_defor.h SID_DEFOR_ERR_INDEX
+# every symbol include/sid_grid.h declares (outlier filter and deformation on a grid of drift vectors, same library)
+GRID_SYMBOLS = ('sid_grid_filter', 'sid_grid_deformation', 'sid_grid_filter_device', 'sid_grid_deformation_device',
+                'sid_grid_last_error', 'sid_grid_release')
+GRID_DIAGONALS = {'shorter': 0, 'main': 1, 'anti': 2}     # SID_GRID_DIAG_*
+GRID_TILE = (8, 32)                                       # SID_GRID_TILE_ROWS, SID_GRID_TILE_COLS: the filter kernel's tile
 
 # every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
 PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
@@ -162,6 +167,15 @@ def lib():
         L.sid_defor_debug_hypot.argtypes = [C.c_int, _f64p, _f64p, C.c_int64, _f64p]
         L.sid_defor_last_error.restype = C.c_char_p
         L.sid_defor_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_grid_filter'):
+        vp = C.c_void_p
+        flt = [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int]
+        L.sid_grid_filter.argtypes = [C.c_int, _f64p, _f64p, _u8p] + flt + [_u8p, _f64p]
+        L.sid_grid_deformation.argtypes = [C.c_int] + [_f64p] * 4 + [_u8p, C.c_int64, C.c_int64, C.c_int] + [_f64p] * 5 + [_i32p]
+        L.sid_grid_filter_device.argtypes = [vp] * 3 + flt + [vp] * 3
+        L.sid_grid_deformation_device.argtypes = [vp] * 5 + [C.c_int64, C.c_int64, C.c_int] + [vp] * 7
+        L.sid_grid_last_error.restype = C.c_char_p
+        L.sid_grid_release.argtypes = [C.c_int]
     if hasattr(L, 'sid_prep_apply'):
         vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
         L.sid_prep_subsample.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, C.c_int64, vp, vp]
@@ -220,14 +234,14 @@ def _p(a, t):
 
 def release_workspaces(device=-1):
     """Hand the cached device memory of the detector, the matcher, the first-guess evaluation and the deformation back
-    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``; -1: every device).  No call on that device may be in flight.
+    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``; -1: every device).  No call on that device may be in flight.
     A process that never loaded the library has nothing cached: this returns without loading it (it is registered with
     atexit through pmlib.release_contexts, and loading means importing torch and initialising the GPU - not at interpreter
     shutdown, and not in a process that only used the host code)."""
     if _lib is None:
         return
     L = _lib
-    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release'):
+    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release'):
         if hasattr(L, name):
             getattr(L, name)(int(device))
 
@@ -763,6 +777,49 @@ def defor_debug_hypot(x, y, device=0):
     out = np.empty_like(x)
     _defor_check(lib().sid_defor_debug_hypot(int(device), _p(x, _f64p), _p(y, _f64p), x.size, _p(out, _f64p)))
     return out
+
+
+def _grid_check(rc):
+    if rc != 0:
+        raise SidPmError(rc, lib().sid_grid_last_error().decode())
+
+
+def _opt_u8(valid):
+    return _p(valid, _u8p) if valid is not None else None
+
+
+def grid_filter(u, v, valid, eps, threshold, radius, min_neighbours, device=0):
+    """``sid_grid_filter`` on host arrays: u, v float64 [rows, cols], valid uint8 [rows, cols] or None (C-contiguous)
+    -> keep uint8 [rows, cols], res float64 [rows, cols].  device=-1: the kernels' source in a host loop (tests)."""
+    rows, cols = u.shape
+    keep, res = np.empty((rows, cols), dtype=np.uint8), np.empty((rows, cols), dtype=np.float64)
+    _grid_check(lib().sid_grid_filter(int(device), _p(u, _f64p), _p(v, _f64p), _opt_u8(valid), rows, cols, float(eps),
+                                      float(threshold), int(radius), int(min_neighbours), _p(keep, _u8p), _p(res, _f64p)))
+    return keep, res
+
+
+def grid_deformation(x, y, u, v, valid, diagonal, device=0):
+    """``sid_grid_deformation`` on host arrays: x, y, u, v float64 [rows, cols] (rows, cols >= 2), valid uint8 or None,
+    diagonal a SID_GRID_DIAG_* code -> e1, e2, e3, a, p float64 [rows-1, cols-1, 2], t int32 [rows-1, cols-1, 2, 3]."""
+    rows, cols = x.shape
+    out = [np.empty((rows - 1, cols - 1, 2), dtype=np.float64) for _ in range(5)]
+    t = np.empty((rows - 1, cols - 1, 2, 3), dtype=np.int32)
+    _grid_check(lib().sid_grid_deformation(int(device), *[_p(a, _f64p) for a in (x, y, u, v)], _opt_u8(valid), rows, cols,
+                                           int(diagonal), *[_p(a, _f64p) for a in out], _p(t, _i32p)))
+    return tuple(out) + (t,)
+
+
+def grid_filter_device(u, v, valid, rows, cols, eps, threshold, radius, min_neighbours, keep, res, stream):
+    """``sid_grid_filter_device`` on raw device pointers (torch ``data_ptr()``; valid 0 for none)."""
+    _grid_check(lib().sid_grid_filter_device(*[C.c_void_p(int(q)) for q in (u, v, valid)], int(rows), int(cols), float(eps),
+                                             float(threshold), int(radius), int(min_neighbours), C.c_void_p(int(keep)),
+                                             C.c_void_p(int(res)), C.c_void_p(int(stream))))
+
+
+def grid_deformation_device(x, y, u, v, valid, rows, cols, diagonal, outs, stream):
+    """``sid_grid_deformation_device`` on raw device pointers: outs = (e1, e2, e3, a, p, t)."""
+    _grid_check(lib().sid_grid_deformation_device(*[C.c_void_p(int(q)) for q in (x, y, u, v, valid)], int(rows), int(cols),
+                                                  int(diagonal), *[C.c_void_p(int(q)) for q in outs], C.c_void_p(int(stream))))
 
 
 def _prep_check(rc):

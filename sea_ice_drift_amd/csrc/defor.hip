@@ -1,7 +1,8 @@
 // defor.hip - sea-ice deformation on gfx950 (C ABI: include/sid_defor.h; the reference's libdefor.py).
 // One thread per triangle: gather the three corners of x, y, u, v, sides, perimeter and Heron's area, the contour integrals,
 // and five structure-of-arrays float64 outputs.  The arithmetic is NumPy's, operation for operation;
-// the side lengths use defor_hypot.h, whose host instance serves the host check of sid_defor_debug_hypot(-1, ...).
+// the element arithmetic is defor_elem.h (shared with drift_grid.hip); the side lengths use defor_hypot.h, whose host instance
+// serves the host check of sid_defor_debug_hypot(-1, ...).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -11,7 +12,7 @@
 
 #include "../../include/sid_defor.h"
 #include "../../include/sid_pm.h"
-#include "defor_hypot.h"
+#include "defor_elem.h"
 
 #define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -26,29 +27,6 @@ int fail(int code, const char *fmt, ...)
 
 constexpr int kBlock = 256;
 constexpr int64_t kMaxElems = (int64_t)0x7fffffff * kBlock;     // grid.x limit
-
-// libdefor.get_deformation_elems for one element: corners c = 0, 1, 2 of x, y, u, v and the area a.
-// The sums start from Python's integer 0 (0 + first term, 0 - first term: a -0.0 term gives +0.0).
-__device__ __forceinline__ void elem(const double x[3], const double y[3], const double u[3], const double v[3], double a,
-                                     double &e1, double &e2, double &e3)
-{
-    double ux = 0.0, uy = 0.0, vx = 0.0, vy = 0.0;
-    const int i0s[3] = {1, 2, 0}, i1s[3] = {0, 1, 2};
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        const int i0 = i0s[s], i1 = i1s[s];
-        ux = ux + (u[i0] + u[i1]) * (y[i0] - y[i1]);
-        uy = uy - (u[i0] + u[i1]) * (x[i0] - x[i1]);
-        vx = vx + (v[i0] + v[i1]) * (y[i0] - y[i1]);
-        vy = vy - (v[i0] + v[i1]) * (x[i0] - x[i1]);
-    }
-    const double a2 = 2.0 * a;
-    ux = ux / a2; uy = uy / a2; vx = vx / a2; vy = vy / a2;
-    e1 = ux + vy;
-    const double d = ux - vy, s = uy + vx;
-    e2 = sqrt(d * d + s * s);                  // ** 2 is x * x, ** 0.5 is sqrt in NumPy
-    e3 = vx - uy;
-}
 
 // Corner index k of a triangle as NumPy's fancy indexing reads it: i < 0 wraps once; outside [0, n) is an error
 template <typename I>
@@ -82,15 +60,8 @@ __global__ __launch_bounds__(kBlock) void k_defor_tri(const double *__restrict__
     double xs[3], ys[3], us[3], vs[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) { xs[j] = x[c[j]]; ys[j] = y[c[j]]; us[j] = u[c[j]]; vs[j] = v[c[j]]; }
-    // np.diff(np.vstack([xt, xt[0]]), axis=0): corner1 - corner0, corner2 - corner1, corner0 - corner2
-    const double s0 = sid_defor::hypot64(xs[1] - xs[0], ys[1] - ys[0]);
-    const double s1 = sid_defor::hypot64(xs[2] - xs[1], ys[2] - ys[1]);
-    const double s2 = sid_defor::hypot64(xs[0] - xs[2], ys[0] - ys[2]);
-    const double p = (s0 + s1) + s2;
-    const double h = p / 2.0;
-    const double a = sqrt(((h * (h - s0)) * (h - s1)) * (h - s2));
-    double r1, r2, r3;
-    elem(xs, ys, us, vs, a, r1, r2, r3);
+    double r1, r2, r3, a, p;
+    sid_defor::triangle(xs, ys, us, vs, r1, r2, r3, a, p);
     e1[k] = r1; e2[k] = r2; e3[k] = r3; ao[k] = a; po[k] = p;
 }
 
@@ -106,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void k_defor_elems(const double *__restrict
 #pragma unroll
     for (int j = 0; j < 3; ++j) { xs[j] = x[j * m + k]; ys[j] = y[j * m + k]; us[j] = u[j * m + k]; vs[j] = v[j * m + k]; }
     double r1, r2, r3;
-    elem(xs, ys, us, vs, a[k], r1, r2, r3);
+    sid_defor::elem(xs, ys, us, vs, a[k], r1, r2, r3);
     e1[k] = r1; e2[k] = r2; e3[k] = r3;
 }
 

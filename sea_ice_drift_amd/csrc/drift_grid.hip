@@ -1,0 +1,357 @@
+// drift_grid.hip - drift grids on gfx950 (C ABI: include/sid_grid.h): the normalised median test and the
+// deformation on the grid's own triangles.  The per-node and per-cell arithmetic is grid_cell.h / defor_elem.h, compiled here
+// for the device and for the host instance (device = -1) alike.
+//   k_grid_filter  one thread per node, 8 x 32 node tiles; the tile and its halo (u, v; NaN in both where a node is unusable or
+//                  outside the grid) are staged in LDS once, and the four medians come by rank selection over the <= 24
+//                  neighbours read from there: no per-thread array.
+//   k_grid_defor   one thread per cell: the four ring nodes of x, y, u, v, the triangle rule, two slots written
+//                  structure-of-arrays.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <mutex>
+
+#include "../../include/sid_grid.h"
+#include "../../include/sid_pm.h"
+#include "grid_cell.h"
+
+#define SID_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+thread_local char g_err[256] = "";
+int fail(int code, const char *fmt, ...)
+{
+    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
+    return code;
+}
+
+constexpr int kTR = SID_GRID_TILE_ROWS, kTC = SID_GRID_TILE_COLS, kBlock = kTR * kTC;
+static_assert(kBlock == 256, "the filter's tile is one 256-thread workgroup");
+
+// ---------------------------------------------------------------- filter
+// Neighbour (di, dj) of the node at (li, lj) of the staged tile
+struct LdsGet {
+    const double *su, *sv;
+    int pitch, li, lj;
+    __device__ __forceinline__ void operator()(int di, int dj, double &a, double &b) const
+    {
+        const int o = (li + di) * pitch + (lj + dj);
+        a = su[o]; b = sv[o];
+    }
+};
+
+// The same from the arrays themselves, for the host instance
+struct HostGet {
+    const double *u, *v;
+    const uint8_t *valid;
+    int64_t rows, cols, r, c;
+    void operator()(int di, int dj, double &a, double &b) const
+    {
+        const int64_t rr = r + di, cc = c + dj;
+        a = NAN; b = NAN;
+        if (rr < 0 || rr >= rows || cc < 0 || cc >= cols) return;
+        const int64_t k = rr * cols + cc;
+        if (sid_grid::usable_uv(valid, k, u[k], v[k])) { a = u[k]; b = v[k]; }
+    }
+};
+
+size_t filter_lds_bytes(int radius) { return sizeof(double) * 2 * (size_t)(kTR + 2 * radius) * (size_t)(kTC + 2 * radius); }
+
+__global__ __launch_bounds__(kBlock) void k_grid_filter(const double *__restrict__ u, const double *__restrict__ v,
+                                                        const uint8_t *__restrict__ valid, int64_t rows, int64_t cols,
+                                                        int64_t tiles_c, double eps, double threshold, int radius,
+                                                        int min_neighbours, uint8_t *__restrict__ keep, double *__restrict__ res)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int hh = kTR + 2 * radius, hw = kTC + 2 * radius;
+    double *su = reinterpret_cast<double *>(smem), *sv = su + hh * hw;
+    const int64_t tile = blockIdx.x, tr = tile / tiles_c, tc = tile - tr * tiles_c;
+    const int64_t r0 = tr * kTR - radius, c0 = tc * kTC - radius;
+    for (int e = threadIdx.x; e < hh * hw; e += kBlock) {
+        const int li = e / hw, lj = e - li * hw;
+        const int64_t r = r0 + li, c = c0 + lj;
+        double a = NAN, b = NAN;
+        if (r >= 0 && r < rows && c >= 0 && c < cols) {
+            const int64_t k = r * cols + c;
+            const double uu = u[k], vv = v[k];
+            if (sid_grid::usable_uv(valid, k, uu, vv)) { a = uu; b = vv; }
+        }
+        su[e] = a; sv[e] = b;
+    }
+    __syncthreads();
+    const int ti = threadIdx.x / kTC, tj = threadIdx.x - ti * kTC;
+    const int64_t r = tr * kTR + ti, c = tc * kTC + tj;
+    if (r >= rows || c >= cols) return;
+    const LdsGet get = {su, sv, hw, ti + radius, tj + radius};
+    const int o = (ti + radius) * hw + (tj + radius);
+    uint8_t k8;
+    double rs;
+    sid_grid::filter_node(get, radius, su[o], sv[o], eps, threshold, min_neighbours, k8, rs);
+    keep[r * cols + c] = k8;
+    res[r * cols + c] = rs;
+}
+
+void host_filter(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols, double eps, double threshold,
+                 int radius, int min_neighbours, uint8_t *keep, double *res)
+{
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t c = 0; c < cols; ++c) {
+            const int64_t k = r * cols + c;
+            const HostGet get = {u, v, valid, rows, cols, r, c};
+            const bool ok = sid_grid::usable_uv(valid, k, u[k], v[k]);
+            sid_grid::filter_node(get, radius, ok ? u[k] : NAN, ok ? v[k] : NAN, eps, threshold, min_neighbours, keep[k], res[k]);
+        }
+}
+
+// ---------------------------------------------------------------- deformation
+// Cell k = i (cols - 1) + j of either instance: gather the ring, apply the rule, write both slots
+__host__ __device__ inline void one_cell(const double *x, const double *y, const double *u, const double *v, const uint8_t *valid,
+                                         int64_t cols, int diagonal, int64_t k,
+                                         double *e1, double *e2, double *e3, double *ao, double *po, int32_t *t)
+{
+    const int64_t i = k / (cols - 1), j = k - i * (cols - 1), A = i * cols + j;
+    const int32_t ids[4] = {(int32_t)A, (int32_t)(A + 1), (int32_t)(A + cols + 1), (int32_t)(A + cols)};
+    double xs[4], ys[4], us[4], vs[4];
+    unsigned usable = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t n = ids[q];
+        xs[q] = x[n]; ys[q] = y[n]; us[q] = u[n]; vs[q] = v[n];
+        if (sid_grid::usable_uv(valid, n, us[q], vs[q]) && isfinite(xs[q]) && isfinite(ys[q])) usable |= 1u << q;
+    }
+    double out[5][2];
+    int32_t tt[2][3];
+    sid_grid::cell(xs, ys, us, vs, usable, diagonal, ids, out, tt);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int64_t o = 2 * k + s;
+        e1[o] = out[0][s]; e2[o] = out[1][s]; e3[o] = out[2][s]; ao[o] = out[3][s]; po[o] = out[4][s];
+        t[3 * o] = tt[s][0]; t[3 * o + 1] = tt[s][1]; t[3 * o + 2] = tt[s][2];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_grid_defor(const double *__restrict__ x, const double *__restrict__ y,
+                                                       const double *__restrict__ u, const double *__restrict__ v,
+                                                       const uint8_t *__restrict__ valid, int64_t cols, int diagonal, int64_t cells,
+                                                       double *__restrict__ e1, double *__restrict__ e2, double *__restrict__ e3,
+                                                       double *__restrict__ ao, double *__restrict__ po, int32_t *__restrict__ t)
+{
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k < cells) one_cell(x, y, u, v, valid, cols, diagonal, k, e1, e2, e3, ao, po, t);
+}
+
+// ---------------------------------------------------------------- arguments
+int check_size(int64_t rows, int64_t cols)
+{
+    if (rows < 0 || cols < 0) return fail(SID_PM_ERR_ARG, "bad sizes (rows = %lld, cols = %lld)", (long long)rows, (long long)cols);
+    if (rows > 0 && cols > 0x7fffffffLL / rows)
+        return fail(SID_PM_ERR_UNSUPPORTED, "rows * cols >= 2^31 (rows = %lld, cols = %lld)", (long long)rows, (long long)cols);
+    return SID_PM_OK;
+}
+
+int check_filter_args(const void *u, const void *v, int64_t rows, int64_t cols, double eps, double threshold, int radius,
+                      int min_neighbours, const void *keep, const void *res)
+{
+    if (!isfinite(eps) || eps <= 0.0) return fail(SID_PM_ERR_ARG, "eps must be finite and > 0 (got %g)", eps);
+    if (!isfinite(threshold) || threshold <= 0.0) return fail(SID_PM_ERR_ARG, "threshold must be finite and > 0 (got %g)", threshold);
+    if (radius < 1 || radius > 2) return fail(SID_PM_ERR_ARG, "radius must be 1 or 2 (got %d)", radius);
+    if (min_neighbours < 1 || min_neighbours > (2 * radius + 1) * (2 * radius + 1) - 1)
+        return fail(SID_PM_ERR_ARG, "min_neighbours must be in 1..%d (got %d)", (2 * radius + 1) * (2 * radius + 1) - 1, min_neighbours);
+    if (int rc = check_size(rows, cols)) return rc;
+    if (!u || !v || !keep || !res) return fail(SID_PM_ERR_ARG, "null pointer");
+    return SID_PM_OK;
+}
+
+int check_defor_args(const void *x, const void *y, const void *u, const void *v, int64_t rows, int64_t cols, int diagonal,
+                     const void *e1, const void *e2, const void *e3, const void *a, const void *p, const void *t)
+{
+    if (diagonal != SID_GRID_DIAG_SHORTER && diagonal != SID_GRID_DIAG_MAIN && diagonal != SID_GRID_DIAG_ANTI)
+        return fail(SID_PM_ERR_ARG, "unknown diagonal code %d", diagonal);
+    if (int rc = check_size(rows, cols)) return rc;
+    if (!x || !y || !u || !v || !e1 || !e2 || !e3 || !a || !p || !t) return fail(SID_PM_ERR_ARG, "null pointer");
+    return SID_PM_OK;
+}
+
+// ---------------------------------------------------------------- launches
+#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
+
+int launch_filter(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols, double eps, double threshold,
+                  int radius, int min_neighbours, uint8_t *keep, double *res, hipStream_t st)
+{
+    int rc = SID_PM_OK;
+    const int64_t tiles_r = (rows + kTR - 1) / kTR, tiles_c = (cols + kTC - 1) / kTC;     // rows * cols < 2^31: so is the product
+    hipLaunchKernelGGL(k_grid_filter, dim3((unsigned)(tiles_r * tiles_c)), dim3(kBlock), filter_lds_bytes(radius), st,
+                       u, v, valid, rows, cols, tiles_c, eps, threshold, radius, min_neighbours, keep, res);
+    HIP_TRY(hipGetLastError());
+done:
+    return rc;
+}
+
+int launch_defor(const double *x, const double *y, const double *u, const double *v, const uint8_t *valid, int64_t rows,
+                 int64_t cols, int diagonal, double *e1, double *e2, double *e3, double *a, double *p, int32_t *t, hipStream_t st)
+{
+    int rc = SID_PM_OK;
+    const int64_t cells = (rows - 1) * (cols - 1);
+    hipLaunchKernelGGL(k_grid_defor, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       x, y, u, v, valid, cols, diagonal, cells, e1, e2, e3, a, p, t);
+    HIP_TRY(hipGetLastError());
+done:
+    return rc;
+}
+
+// Per device: a grow-only scratch block for the host-buffer entry points (no hipMalloc / hipFree per call once warm).  Calls
+// are serialised by the mutex.
+struct Dev { unsigned char *blk = nullptr; size_t cap = 0; };
+std::mutex g_mu;
+Dev g_dev[16];
+
+int pick_device(int device, int &prev)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n || device >= 16) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    (void)hipGetDevice(&prev); (void)hipSetDevice(device);
+    return SID_PM_OK;
+}
+
+int reserve(Dev &d, size_t bytes)
+{
+    if (d.cap >= bytes) return SID_PM_OK;
+    if (d.blk) (void)hipFree(d.blk);
+    d.blk = nullptr; d.cap = 0;
+    const size_t want = bytes + bytes / 4;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d.blk), want);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SID_PM_ERR_NOMEM : SID_PM_ERR_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
+    d.cap = want;
+    return SID_PM_OK;
+}
+
+size_t up(size_t b) { return (b + 255) / 256 * 256; }
+
+}  // namespace
+
+SID_EXPORT const char *sid_grid_last_error(void) { return g_err; }
+
+SID_EXPORT int sid_grid_release(int device)
+{
+    std::lock_guard<std::mutex> lock(g_mu);
+    int prev = 0;
+    bool any = false;
+    for (int i = 0; i < 16; ++i) any = any || ((device < 0 || i == device) && g_dev[i].blk);
+    if (!any) return SID_PM_OK;
+    (void)hipGetDevice(&prev);
+    for (int i = 0; i < 16; ++i) {
+        if (device >= 0 && i != device) continue;
+        Dev &d = g_dev[i];
+        if (!d.blk) continue;
+        (void)hipSetDevice(i);
+        (void)hipFree(d.blk);
+        d = Dev();
+    }
+    (void)hipSetDevice(prev);
+    return SID_PM_OK;
+}
+
+SID_EXPORT int sid_grid_filter_device(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,
+                                      double eps, double threshold, int radius, int min_neighbours, uint8_t *keep, double *res,
+                                      void *hip_stream)
+{
+    if (int rc = check_filter_args(u, v, rows, cols, eps, threshold, radius, min_neighbours, keep, res)) return rc;
+    if (rows * cols == 0) return SID_PM_OK;
+    return launch_filter(u, v, valid, rows, cols, eps, threshold, radius, min_neighbours, keep, res,
+                         reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+SID_EXPORT int sid_grid_deformation_device(const double *x, const double *y, const double *u, const double *v, const uint8_t *valid,
+                                           int64_t rows, int64_t cols, int diagonal,
+                                           double *e1, double *e2, double *e3, double *a, double *p, int32_t *t, void *hip_stream)
+{
+    if (int rc = check_defor_args(x, y, u, v, rows, cols, diagonal, e1, e2, e3, a, p, t)) return rc;
+    if (rows < 2 || cols < 2) return SID_PM_OK;
+    return launch_defor(x, y, u, v, valid, rows, cols, diagonal, e1, e2, e3, a, p, t, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+SID_EXPORT int sid_grid_filter(int device, const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,
+                               double eps, double threshold, int radius, int min_neighbours, uint8_t *keep, double *res)
+{
+    if (int rc0 = check_filter_args(u, v, rows, cols, eps, threshold, radius, min_neighbours, keep, res)) return rc0;
+    if (rows * cols == 0) return SID_PM_OK;
+    if (device == -1) {
+        host_filter(u, v, valid, rows, cols, eps, threshold, radius, min_neighbours, keep, res);
+        return SID_PM_OK;
+    }
+    int prev = 0;
+    if (int rc0 = pick_device(device, prev)) return rc0;
+    int rc = SID_PM_OK;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        Dev &d = g_dev[device];
+        const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n, o = up(nb) / 8;
+        double *du, *dres;
+        uint8_t *dvalid, *dkeep;
+        if ((rc = reserve(d, 3 * up(nb) + 2 * up(n)))) goto done;
+        du = reinterpret_cast<double *>(d.blk);                          // u, v, res, then valid, keep
+        dres = du + 2 * o;
+        dvalid = reinterpret_cast<uint8_t *>(du + 3 * o);
+        dkeep = dvalid + up(n);
+        HIP_TRY(hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, 0));
+        HIP_TRY(hipMemcpyAsync(du + o, v, nb, hipMemcpyHostToDevice, 0));
+        if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
+        if ((rc = launch_filter(du, du + o, valid ? dvalid : nullptr, rows, cols, eps, threshold, radius, min_neighbours, dkeep, dres, 0)))
+            goto done;
+        HIP_TRY(hipMemcpyAsync(keep, dkeep, n, hipMemcpyDeviceToHost, 0));
+        HIP_TRY(hipMemcpyAsync(res, dres, nb, hipMemcpyDeviceToHost, 0));
+        HIP_TRY(hipStreamSynchronize(0));
+    }
+done:
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+SID_EXPORT int sid_grid_deformation(int device, const double *x, const double *y, const double *u, const double *v,
+                                    const uint8_t *valid, int64_t rows, int64_t cols, int diagonal,
+                                    double *e1, double *e2, double *e3, double *a, double *p, int32_t *t)
+{
+    if (int rc0 = check_defor_args(x, y, u, v, rows, cols, diagonal, e1, e2, e3, a, p, t)) return rc0;
+    if (rows < 2 || cols < 2) return SID_PM_OK;
+    if (device == -1) {
+        for (int64_t k = 0; k < (rows - 1) * (cols - 1); ++k) one_cell(x, y, u, v, valid, cols, diagonal, k, e1, e2, e3, a, p, t);
+        return SID_PM_OK;
+    }
+    int prev = 0;
+    if (int rc0 = pick_device(device, prev)) return rc0;
+    int rc = SID_PM_OK;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        Dev &d = g_dev[device];
+        const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n, o = up(nb) / 8;
+        const size_t m2 = 2 * (size_t)((rows - 1) * (cols - 1)), mb = sizeof(double) * m2, om = up(mb) / 8, tb = sizeof(int32_t) * 3 * m2;
+        double *in, *out;
+        int32_t *dt;
+        uint8_t *dvalid;
+        if ((rc = reserve(d, 4 * up(nb) + 5 * up(mb) + up(tb) + up(n)))) goto done;
+        in = reinterpret_cast<double *>(d.blk);                          // x, y, u, v, then e1, e2, e3, a, p, then t, then valid
+        out = in + 4 * o;
+        dt = reinterpret_cast<int32_t *>(out + 5 * om);
+        dvalid = reinterpret_cast<uint8_t *>(dt) + up(tb);
+        {
+            const double *src[4] = {x, y, u, v};
+            for (int j = 0; j < 4; ++j) HIP_TRY(hipMemcpyAsync(in + j * o, src[j], nb, hipMemcpyHostToDevice, 0));
+        }
+        if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
+        if ((rc = launch_defor(in, in + o, in + 2 * o, in + 3 * o, valid ? dvalid : nullptr, rows, cols, diagonal,
+                               out, out + om, out + 2 * om, out + 3 * om, out + 4 * om, dt, 0)))
+            goto done;
+        {
+            double *dst[5] = {e1, e2, e3, a, p};
+            for (int j = 0; j < 5; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out + j * om, mb, hipMemcpyDeviceToHost, 0));
+        }
+        HIP_TRY(hipMemcpyAsync(t, dt, tb, hipMemcpyDeviceToHost, 0));
+        HIP_TRY(hipStreamSynchronize(0));
+    }
+done:
+    (void)hipSetDevice(prev);
+    return rc;
+}

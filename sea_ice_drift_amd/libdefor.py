@@ -3,7 +3,9 @@
 The per-element pass - corners, sides, perimeter, area, contour integrals, divergence / shear / vorticity - is one HIP kernel
 (include/sid_defor.h, csrc/defor.hip) that repeats NumPy's float64 arithmetic operation for operation, so the outputs are the
 reference's bit for bit.  The triangulation of ``get_deformation_nodes`` stays the reference's own
-call, ``matplotlib.tri.Triangulation`` on the host: its triangles and their order are Qhull's.
+call, ``matplotlib.tri.Triangulation`` on the host: its triangles and their order are Qhull's.  ``get_deformation_grid`` (not
+the reference's) needs no triangulation: it takes the 2-D grids ``get_drift_PM`` returns and splits every cell in two
+(include/sid_grid.h, csrc/drift_grid.hip).
 
 NumPy arrays in give NumPy arrays out (the call copies to and from device ``device``).  float64 torch tensors on a ROCm
 device give tensors on that device out, computed on the caller's current stream with no copy to the host (the call waits for
@@ -18,7 +20,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ['get_deformation_elems', 'get_deformation_on_triangulation', 'get_deformation_nodes']
+__all__ = ['get_deformation_elems', 'get_deformation_on_triangulation', 'get_deformation_nodes', 'get_deformation_grid']
 
 
 def _is_tensor(a):
@@ -39,11 +41,11 @@ def _dtype_name(a):
     return str(a.dtype).replace('torch.', '')
 
 
-def _need_f64(names, arrays):
+def _need_f64(names, arrays, who='libdefor'):
     for name, a in zip(names, arrays):
         if _dtype_name(a) != 'float64':
-            raise NotImplementedError('libdefor: %s is %s; only float64 inputs are implemented (NumPy rounds float32 or mixed '
-                                      'inputs differently)' % (name, _dtype_name(a)))
+            raise NotImplementedError('%s: %s is %s; only float64 inputs are implemented (NumPy rounds float32 or mixed '
+                                      'inputs differently)' % (who, name, _dtype_name(a)))
 
 
 def _node_arrays(x, y, u, v):
@@ -70,12 +72,48 @@ def _triangles(t, n):
         raise ValueError('libdefor: t must be (M, 3), one row of node indices per triangle (got shape %s)' % (tuple(t.shape),))
 
 
-def _device_of(arrays):
+def _device_of(arrays, who='libdefor'):
     dev = arrays[0].device
     for a in arrays:
         if a.device != dev or a.device.type != 'cuda':
-            raise TypeError('libdefor: tensors must all be on one ROCm device (got %s)' % [str(b.device) for b in arrays])
+            raise TypeError('%s: tensors must all be on one ROCm device (got %s)' % (who, [str(b.device) for b in arrays]))
     return dev
+
+
+def _grid_inputs(who, names, arrays, valid, device):
+    """The checks the two grid functions share (this one and libfilter.normalized_median_test): float64 2-D arrays of one
+    shape, `valid` bool or uint8 of that shape or None, all NumPy or all tensors on one ROCm device.
+    -> kind, arrays, valid (uint8 or None; C-contiguous all), the tensors' device (None for NumPy)."""
+    given = tuple(arrays) + ((valid,) if valid is not None else ())
+    flags = [_is_tensor(a) for a in given]
+    if any(flags) and not all(flags):
+        raise TypeError('%s: pass either torch tensors on one ROCm device or NumPy arrays, not a mix' % who)
+    kind = 'tensor' if flags[0] else 'numpy'
+    if kind == 'numpy':
+        arrays = [np.asarray(a) for a in arrays]
+        valid = np.asarray(valid) if valid is not None else None
+    _need_f64(names, arrays, who)
+    shapes = [tuple(a.shape) for a in arrays]
+    if len(shapes[0]) != 2 or any(s != shapes[0] for s in shapes):
+        raise ValueError('%s: %s must be 2-D arrays of one shape (rows, cols) (got shapes %s)' % (who, ', '.join(names), shapes))
+    if valid is not None:
+        if _dtype_name(valid) not in ('bool', 'uint8'):
+            raise TypeError('%s: valid is %s; it must be bool or uint8' % (who, _dtype_name(valid)))
+        if tuple(valid.shape) != shapes[0]:
+            raise ValueError('%s: valid must have the shape of the grids, %s (got %s)' % (who, shapes[0], tuple(valid.shape)))
+    if kind == 'numpy':
+        if int(device) < 0:
+            raise ValueError('%s: device must be a HIP device index >= 0 (got %d)' % (who, int(device)))
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        if valid is not None:
+            valid = np.ascontiguousarray(valid).view(np.uint8)
+        return kind, arrays, valid, None
+    import torch
+    dev = _device_of(given, who)
+    arrays = [a.contiguous() for a in arrays]
+    if valid is not None:
+        valid = valid.contiguous().view(torch.uint8)
+    return kind, arrays, valid, dev
 
 
 def get_deformation_elems(x, y, u, v, a, device=0):
@@ -170,3 +208,42 @@ def get_deformation_nodes(x, y, u, v, device=0):
         t = tri.triangles
     e1, e2, e3, a, p = get_deformation_on_triangulation(x, y, u, v, t, device=device)
     return e1, e2, e3, a, p, t
+
+
+def get_deformation_grid(x, y, u, v, valid=None, diagonal='shorter', device=0):
+    """Deformation on the grid's own triangles: every cell of a (R, C) grid of drift vectors is split in two, no triangulation
+    (not the reference's; specification: include/sid_grid.h).
+
+    x, y : (R, C) float64 node coordinates, m;  u, v : (R, C) float64 node velocities, m/s - the grids as get_drift_PM returns
+           them, NaN where there is no result
+    valid : (R, C) bool or uint8, or None.  A node takes part when valid (or no mask) and x, y, u, v are finite - e.g. the
+            ``keep`` of libfilter.normalized_median_test
+    diagonal : 'shorter' (the shorter diagonal of each cell - the Delaunay one of a parallelogram; ties take the main one),
+               'main' ((i, j) - (i+1, j+1)) or 'anti' ((i, j+1) - (i+1, j))
+    device : HIP device of a NumPy call (tensors run on their own device).
+
+    A cell with four usable nodes holds two triangles, one with three holds one (slot 0), fewer none; triangles are
+    counter-clockwise.  Each triangle's values are get_deformation_on_triangulation's on its three nodes.
+
+    Returns e1, e2, e3, a, p (R-1, C-1, 2) float64 - NaN where a slot holds no triangle - and t (R-1, C-1, 2, 3) int32, flat
+    node numbers (row * C + column), -1 there.  NumPy in gives NumPy out; tensors give tensors on their device, computed on the
+    caller's current stream with no wait and no copy to the host."""
+    if diagonal not in _capi.GRID_DIAGONALS:
+        raise ValueError("libdefor: diagonal must be 'shorter', 'main' or 'anti' (got %r)" % (diagonal,))
+    kind, (x, y, u, v), valid, dev = _grid_inputs('libdefor', ('x', 'y', 'u', 'v'), (x, y, u, v), valid, device)
+    rows, cols = x.shape
+    shape = (max(rows - 1, 0), max(cols - 1, 0), 2)
+    code = _capi.GRID_DIAGONALS[diagonal]
+    if kind == 'numpy':
+        if shape[0] * shape[1] == 0:
+            return tuple(np.empty(shape, dtype=np.float64) for _ in range(5)) + (np.empty(shape + (3,), dtype=np.int32),)
+        return _capi.grid_deformation(x, y, u, v, valid, code, device=device)
+    import torch
+    outs = tuple(torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(5)) + (
+        torch.empty(shape + (3,), dtype=torch.int32, device=dev),)
+    if shape[0] * shape[1]:
+        with torch.cuda.device(dev):
+            _capi.grid_deformation_device(x.data_ptr(), y.data_ptr(), u.data_ptr(), v.data_ptr(),
+                                          valid.data_ptr() if valid is not None else 0, rows, cols, code,
+                                          [o.data_ptr() for o in outs], torch.cuda.current_stream(dev).cuda_stream)
+    return outs
