@@ -52,6 +52,25 @@ int sid_fg_nearest_dist(int device, const double *seeds, int64_t n_seeds, const 
  * the same buckets (sqrt of the exact integer squared distance in float64: the same numbers). */
 int sid_fg_distance_image(int device, const double *seeds, int64_t n_seeds, int64_t rows, int64_t cols, double *dist);
 
+/* A first guess that needs no triangulation (NOT the reference's method): out [n_q][2] = the
+ * component-wise median of values [n_seeds][2] over the k nearest seeds [n_seeds][2] of every query q [n_q][2].  Every
+ * operation below is one IEEE double rounding in the order written (tests/fg_knn_spec.py restates it in NumPy).
+ *   usable seed     both coordinates and both values finite; no other seed takes part.
+ *   distance        dx = q0 - s0; dy = q1 - s1; d2 = dx*dx + dy*dy.
+ *   admissible      d2 <= m2, m2 = max_dist * max_dist (max_dist = +inf: no limit).
+ *   neighbours      the first m = min(k, number of admissible usable seeds) seeds in ascending (d2, seed index) order -
+ *                   lexicographic, so ties and duplicated seeds resolve by index.
+ *   result          per component the median of the neighbours' values: m odd - the middle value of the sorted values s;
+ *                   m even - (s[m/2-1] + s[m/2]) / 2.0.  m = 0, or a query that is not finite: NaN, NaN.
+ *   count  [n_q]    (may be NULL) m.       index [n_q][k]   (may be NULL) the neighbours in that order, padded with -1.
+ * n_q = 0 returns at once; n_seeds = 0 is valid (every result empty).  SID_PM_ERR_ARG: seeds NULL with n_seeds > 0, values, q
+ * or out NULL, a negative size, k outside 1..16, max_dist NaN or <= 0; SID_PM_ERR_UNSUPPORTED: n_seeds >= 2^31; all before any
+ * device call.  device = -1 runs the host instance: the same source (csrc/fg_knn.h) in a loop over every (query, seed) pair.
+ * On a device the queries walk the buckets of sid_fg_nearest_dist (fewer than 256 usable seeds, a bounding box without area
+ * or SID_FG_NO_GRID=1: every pair); the result is the host instance's bit for bit either way. */
+int sid_fg_knn(int device, const double *seeds, int64_t n_seeds, const double *values, const double *q, int64_t n_q,
+               int k, double max_dist, double *out, int32_t *count, int32_t *index);
+
 const char *sid_fg_last_error(void);
 /* Free the grow-only device scratch block of the two entry points on `device` (every device: -1).  The blocks are kept between calls so that no call pays for
  * hipMalloc / hipFree; a long-lived process that is done with the GPU hands the memory back with this (the Python mirror's

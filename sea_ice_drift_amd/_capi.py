@@ -40,7 +40,7 @@ STAGE_SYMBOLS = ('sid_stage_create', 'sid_stage_destroy', 'sid_stage_begin', 'si
 ORB_SYMBOLS = ('sid_orb_detect', 'sid_orb_last_error', 'sid_orb_release')
 
 # every symbol include/sid_fg.h declares (first-guess evaluation, same library)
-FG_SYMBOLS = ('sid_fg_interp_linear', 'sid_fg_nearest_dist', 'sid_fg_distance_image', 'sid_fg_last_error', 'sid_fg_release')
+FG_SYMBOLS = ('sid_fg_interp_linear', 'sid_fg_nearest_dist', 'sid_fg_distance_image', 'sid_fg_knn', 'sid_fg_last_error', 'sid_fg_release')
 
 # every symbol include/sid_defor.h declares (deformation on a triangulation, same library)
 DEFOR_SYMBOLS = ('sid_defor_triangulation', 'sid_defor_elems', 'sid_defor_triangulation_device', 'sid_defor_elems_device',
@@ -157,6 +157,8 @@ def lib():
     L.sid_fg_nearest_dist.argtypes = [C.c_int, _f64p, C.c_int64, _f64p, C.c_int64, _f64p]
     if hasattr(L, 'sid_fg_distance_image'):
         L.sid_fg_distance_image.argtypes = [C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int64, _f64p]
+    if hasattr(L, 'sid_fg_knn'):                 # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        L.sid_fg_knn.argtypes = [C.c_int, _f64p, C.c_int64, _f64p, _f64p, C.c_int64, C.c_int, C.c_double, _f64p, _i32p, _i32p]
     L.sid_fg_last_error.restype = C.c_char_p
     if hasattr(L, 'sid_defor_triangulation'):
         vp = C.c_void_p
@@ -726,6 +728,28 @@ def fg_distance_image(seeds, rows, cols, device=0):
     if rc != 0:
         raise SidPmError(rc, L.sid_fg_last_error().decode())
     return out
+
+
+def fg_knn(seeds, values, q, k=5, max_dist=None, device=0, details=False):
+    """Component-wise median of values [n,2] over the k nearest of seeds [n,2] at every point of q [m,2] -> [m,2]
+    (include/sid_fg.h sid_fg_knn; not the reference's method).  ``max_dist``: seeds further away do not count (None: no
+    limit); a query without a neighbour gives NaN.  Seeds with a non-finite coordinate or value never take part.
+    ``device=-1``: the kernels' source in a host loop (tests, machines without a GPU).  details=True: also the number of
+    neighbours per query, int32 [m], and their seed indices in ascending (distance, index) order, int32 [m,k] padded with -1."""
+    seeds, values, q = _f64(seeds).reshape(-1, 2), _f64(values).reshape(-1, 2), _f64(q).reshape(-1, 2)
+    if len(values) != len(seeds):
+        raise ValueError('seeds and values differ in length')
+    k = int(k)
+    out = np.empty((len(q), 2), dtype=np.float64)
+    cnt = np.empty(len(q), dtype=np.int32)
+    idx = np.empty((len(q), min(max(k, 0), 16)), dtype=np.int32)
+    L = lib()
+    rc = L.sid_fg_knn(int(device), _p(seeds, _f64p), len(seeds), _p(values, _f64p), _p(q, _f64p), len(q), k,
+                      float('inf') if max_dist is None else float(max_dist), _p(out, _f64p),
+                      _p(cnt, _i32p) if details else None, _p(idx, _i32p) if details else None)
+    if rc != 0:
+        raise SidPmError(rc, L.sid_fg_last_error().decode())
+    return (out, cnt, idx) if details else out
 
 
 def _defor_check(rc):

@@ -3,7 +3,9 @@
 // Point location walks a uniform grid of buckets (round 4): every simplex is listed in the cells its bounding box touches, a
 // query tests the simplices of its own cell only - a dozen instead of all 6 x 10^4 (rounds 2-3: brute force over (query,
 // simplex) pairs, 1.7 ms per call; kept as the fallback for triangulations whose bucket lists would not fit).  The
-// nearest-key-point distance is brute force over (query, seed) pairs with the seeds staged through LDS.
+// nearest-key-point distance is brute force over (query, seed) pairs with the seeds staged through LDS, or (round 5) a ring
+// walk over buckets of seeds; sid_fg_knn - the k nearest seeds and the median of their values, a first guess that needs no
+// triangulation - walks the same buckets with the list arithmetic of fg_knn.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <float.h>
@@ -11,9 +13,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <mutex>
+#include <vector>
 
 #include "../../include/sid_fg.h"
 #include "../../include/sid_pm.h"
+#include "fg_knn.h"
 
 #define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -355,6 +359,90 @@ __global__ __launch_bounds__(256) void k_nearest_grid(const double *seeds, const
     dist[i] = sqrt(best);
 }
 
+// ---- the k nearest seeds and the median of their values (sid_fg_knn; fg_knn.h) ----
+// Both kernels: one thread per query, the neighbour list in registers (capacity K >= k: its first k pairs are the k best), the
+// seeds are the USABLE ones only (the host compacts them, in order, before the upload: index order is kept).
+// k_knn: every seed, staged through LDS as in k_nearest - the definition.
+template <int K>
+__global__ __launch_bounds__(256) void k_knn(const double *seeds, const double *values, int64_t ns, const double *q, int64_t nq, int k, double m2,
+                                             double *out, int32_t *count, int32_t *index)
+{
+    __shared__ double sx[1024], sy[1024];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const double x = i < nq ? q[2 * i] : NAN, y = i < nq ? q[2 * i + 1] : NAN;
+    const bool live = isfinite(x) && isfinite(y);
+    sid_knn::List<K> l;
+    sid_knn::clear(l);
+    for (int64_t base = 0; base < ns; base += 1024) {
+        __syncthreads();
+        for (int s = threadIdx.x; s < 1024 && base + s < ns; s += 256) { sx[s] = seeds[2 * (base + s)]; sy[s] = seeds[2 * (base + s) + 1]; }
+        __syncthreads();
+        const int n = (int)((ns - base) < 1024 ? (ns - base) : 1024);
+        if (live)
+            for (int s = 0; s < n; ++s) sid_knn::offer(l, sid_knn::dist2(x, y, sx[s], sy[s]), (int32_t)(base + s), m2);
+    }
+    if (i < nq) sid_knn::finish<K>(l, values, k, out + 2 * i, count + i, index + i * k);
+}
+// k_knn_grid: the ring walk of k_nearest_grid over the same buckets.  The walk ends when the block covers the grid, or when
+// no seed outside the block can enter the first k pairs: such a seed is more than `lb` away (lb already reduced by the margin
+// that covers the rounding of cell_of, so strictly more - a tie with the k-th pair is impossible), hence out when the list
+// holds k pairs and the k-th d2 <= lb lb, or when lb lb > m2 (not admissible).  The candidates seen are a superset of those
+// that can enter, each scored by the expression of k_knn, and the order of the list is (d2, index) whatever the order of a
+// bucket's entries: the result is that of k_knn bit for bit.
+template <int K>
+__global__ __launch_bounds__(256) void k_knn_grid(const double *seeds, const double *values, const int32_t *start, const int32_t *ids, GridGeo g,
+                                                  double wx, double wy, double margin, const double *q, int64_t nq, int k, double m2,
+                                                  double *out, int32_t *count, int32_t *index)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const double x = q[2 * i], y = q[2 * i + 1];
+    sid_knn::List<K> l;
+    sid_knn::clear(l);
+    if (isfinite(x) && isfinite(y)) {                                  // (cell_of is never reached with a NaN)
+        const int cx = cell_of(x, g.x0, g.ix), cy = cell_of(y, g.y0, g.iy);
+        for (int r = 0; r < kGrid; ++r) {
+            const int xa = cx - r, xb = cx + r, ya = cy - r, yb = cy + r;
+            auto visit = [&](int cell) {
+                for (int32_t e = start[cell]; e < start[cell + 1]; ++e) {
+                    const int32_t s = ids[e];
+                    sid_knn::offer(l, sid_knn::dist2(x, y, seeds[2 * s], seeds[2 * s + 1]), s, m2);
+                }
+            };
+            const int x_lo = xa < 0 ? 0 : xa, x_hi = xb > kGrid - 1 ? kGrid - 1 : xb;
+            for (int yy = (ya < 0 ? 0 : ya); yy <= (yb > kGrid - 1 ? kGrid - 1 : yb); ++yy) {
+                if (yy == ya || yy == yb) {
+                    for (int xx = x_lo; xx <= x_hi; ++xx) visit(yy * kGrid + xx);
+                } else {
+                    if (xa >= 0) visit(yy * kGrid + xa);
+                    if (xb <= kGrid - 1) visit(yy * kGrid + xb);
+                }
+            }
+            double lb = INFINITY;
+            if (xa > 0) lb = fmin(lb, x - (g.x0 + (double)xa * wx));
+            if (xb < kGrid - 1) lb = fmin(lb, (g.x0 + (double)(xb + 1) * wx) - x);
+            if (ya > 0) lb = fmin(lb, y - (g.y0 + (double)ya * wy));
+            if (yb < kGrid - 1) lb = fmin(lb, (g.y0 + (double)(yb + 1) * wy) - y);
+            if (lb == INFINITY) break;                                 // the block covers the grid
+            lb -= margin;
+            const double lb2 = lb * lb;
+            if (lb > 0.0 && lb2 < INFINITY && (lb2 > m2 || sid_knn::full_within(l, k, lb2))) break;
+        }
+    }
+    sid_knn::finish<K>(l, values, k, out + 2 * i, count + i, index + i * k);
+}
+struct KnnArgs {
+    const double *seeds, *values, *q; int64_t ns, nq; int k; double m2; double *out; int32_t *count, *index;
+    const int32_t *start, *ids; GridGeo g; double wx, wy, margin;    // start == nullptr: every seed (k_knn)
+};
+template <int K>
+void knn_launch(const KnnArgs &a)
+{
+    const dim3 blocks((unsigned)((a.nq + 255) / 256));
+    if (a.start) hipLaunchKernelGGL(k_knn_grid<K>, blocks, dim3(256), 0, 0, a.seeds, a.values, a.start, a.ids, a.g, a.wx, a.wy, a.margin, a.q, a.nq, a.k, a.m2, a.out, a.count, a.index);
+    else hipLaunchKernelGGL(k_knn<K>, blocks, dim3(256), 0, 0, a.seeds, a.values, a.ns, a.q, a.nq, a.k, a.m2, a.out, a.count, a.index);
+}
+
 #define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
 
 // Device scratch of the two entry points: one grow-only block per device, carved per call (no hipMalloc / hipFree per
@@ -562,5 +650,104 @@ static int nearest_dist_impl(int device, const double *seeds, int64_t n_seeds, c
     HIP_TRY(hipMemcpy(dist, d_d, sizeof(double) * n_q, hipMemcpyDeviceToHost));
 done:
     (void)hipSetDevice(prev);
+    return rc;
+}
+
+// The k nearest usable seeds of every query and the component-wise median of their values (sid_fg.h).
+SID_EXPORT int sid_fg_knn(int device, const double *seeds, int64_t n_seeds, const double *values, const double *q, int64_t n_q,
+                          int k, double max_dist, double *out, int32_t *count, int32_t *index)
+{
+    if (n_q == 0) return SID_PM_OK;
+    if (n_seeds < 0 || n_q < 0 || (!seeds && n_seeds > 0) || !values || !q || !out) return fail(SID_PM_ERR_ARG, "bad argument (null pointer or negative size)");
+    if (k < 1 || k > sid_knn::kMaxK) return fail(SID_PM_ERR_ARG, "k = %d outside 1..%d", k, sid_knn::kMaxK);
+    if (!(max_dist > 0.0)) return fail(SID_PM_ERR_ARG, "max_dist must be positive (+inf: no limit)");
+    if (n_seeds >= (int64_t)1 << 31) return fail(SID_PM_ERR_UNSUPPORTED, "n_seeds = %lld: seed indices are 32-bit", (long long)n_seeds);
+    const double m2 = max_dist * max_dist;
+    // The usable seeds (finite coordinates and values), their bounding box, and - only when some seed is not usable - a compacted
+    // copy in the same order with the map back to the caller's indices: no other seed reaches a kernel or a bucket.
+    int64_t n_use = 0;
+    double x_lo = INFINITY, x_hi = -INFINITY, y_lo = INFINITY, y_hi = -INFINITY;
+    for (int64_t s = 0; s < n_seeds; ++s)
+        if (isfinite(seeds[2 * s]) && isfinite(seeds[2 * s + 1]) && isfinite(values[2 * s]) && isfinite(values[2 * s + 1])) {
+            ++n_use;
+            x_lo = fmin(x_lo, seeds[2 * s]); x_hi = fmax(x_hi, seeds[2 * s]); y_lo = fmin(y_lo, seeds[2 * s + 1]); y_hi = fmax(y_hi, seeds[2 * s + 1]);
+        }
+    std::vector<double> cs, cv;
+    std::vector<int32_t> map;
+    std::vector<int32_t> h_count, h_index;
+    if (n_use < n_seeds) {
+        try { cs.reserve(2 * n_use + 2); cv.reserve(2 * n_use + 2); map.reserve(n_use + 1); } catch (...) { return fail(SID_PM_ERR_NOMEM, "host allocation failed"); }
+        for (int64_t s = 0; s < n_seeds; ++s)
+            if (isfinite(seeds[2 * s]) && isfinite(seeds[2 * s + 1]) && isfinite(values[2 * s]) && isfinite(values[2 * s + 1])) {
+                cs.push_back(seeds[2 * s]); cs.push_back(seeds[2 * s + 1]); cv.push_back(values[2 * s]); cv.push_back(values[2 * s + 1]);
+                map.push_back((int32_t)s);
+            }
+        seeds = cs.data(); values = cv.data();
+    }
+    // count and index are always computed; where the caller passed none they go to scratch (the device's own, for index)
+    try {
+        if (!count) { h_count.resize(n_q); count = h_count.data(); }
+        if (!index && (device == -1 || n_use == 0)) { h_index.resize((size_t)n_q * k); index = h_index.data(); }
+    } catch (...) { return fail(SID_PM_ERR_NOMEM, "host allocation failed"); }
+    int prev = 0;
+    int rc = SID_PM_OK;
+    if (device == -1) {
+        for (int64_t i = 0; i < n_q; ++i) sid_knn::brute(seeds, values, n_use, q[2 * i], q[2 * i + 1], k, m2, out + 2 * i, count + i, index + i * k);
+    } else {
+        if (int rc0 = pick_device(device, prev)) return rc0;
+        if (n_use == 0) {                                               // nothing to search: every result is empty
+            for (int64_t i = 0; i < n_q; ++i) { out[2 * i] = NAN; out[2 * i + 1] = NAN; count[i] = 0; for (int j = 0; j < k; ++j) index[i * k + j] = -1; }
+            (void)hipSetDevice(prev);
+            return SID_PM_OK;
+        }
+        std::lock_guard<std::mutex> lock(g_pool_mu);
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        unsigned char *blk = nullptr;
+        KnnArgs a{};
+        double *d_s = nullptr, *d_v = nullptr, *d_q = nullptr, *d_out = nullptr;
+        int32_t *d_count = nullptr, *d_index = nullptr, *d_cnt = nullptr, *d_start = nullptr, *d_ids = nullptr;
+        const double w = x_hi - x_lo, h = y_hi - y_lo;
+        const bool grid = getenv("SID_FG_NO_GRID") == nullptr && n_use >= 256 && w > 0.0 && h > 0.0 && isfinite(w) && isfinite(h);
+        if ((rc = pool_reserve(device, up(sizeof(double) * 2 * n_use) * 2 + up(sizeof(double) * 2 * n_q) * 2 + up(sizeof(int32_t) * n_q) +
+                                       up(sizeof(int32_t) * n_q * k) + up(sizeof(int32_t) * (kGrid * kGrid + 1)) * 2 + up(sizeof(int32_t) * n_use), &blk))) {
+            (void)hipSetDevice(prev);
+            return rc;
+        }
+        {
+            Carver cv2(blk);
+            d_s = cv2.take<double>(2 * n_use); d_v = cv2.take<double>(2 * n_use); d_q = cv2.take<double>(2 * n_q); d_out = cv2.take<double>(2 * n_q);
+            d_count = cv2.take<int32_t>(n_q); d_index = cv2.take<int32_t>((size_t)n_q * k);
+            d_cnt = cv2.take<int32_t>(kGrid * kGrid + 1); d_start = cv2.take<int32_t>(kGrid * kGrid + 1); d_ids = cv2.take<int32_t>(n_use);
+        }
+        HIP_TRY(hipMemcpyAsync(d_s, seeds, sizeof(double) * 2 * n_use, hipMemcpyHostToDevice, 0));
+        HIP_TRY(hipMemcpyAsync(d_v, values, sizeof(double) * 2 * n_use, hipMemcpyHostToDevice, 0));
+        HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
+        a.seeds = d_s; a.values = d_v; a.q = d_q; a.ns = n_use; a.nq = n_q; a.k = k; a.m2 = m2; a.out = d_out; a.count = d_count; a.index = d_index;
+        if (grid) {
+            // the buckets of sid_fg_nearest_dist: same geometry, same binning kernels, same margin
+            const unsigned nb = (unsigned)((n_use + 255) / 256);
+            a.g = GridGeo{x_lo, y_lo, (double)kGrid / w, (double)kGrid / h};
+            a.wx = w / kGrid; a.wy = h / kGrid;
+            a.margin = 1e-9 * (w + h) + 1e-12 * (fabs(x_lo) + fabs(x_hi) + fabs(y_lo) + fabs(y_hi));
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
+            hipLaunchKernelGGL(k_seed_bin<0>, dim3(nb), dim3(256), 0, 0, d_s, n_use, a.g, d_cnt, (const int32_t *)nullptr, (int32_t *)nullptr);
+            hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
+            hipLaunchKernelGGL(k_seed_bin<1>, dim3(nb), dim3(256), 0, 0, d_s, n_use, a.g, d_cnt, d_start, d_ids);
+            a.start = d_start; a.ids = d_ids;
+        }
+        if (k == 1) knn_launch<1>(a);
+        else if (k <= 4) knn_launch<4>(a);
+        else if (k <= 8) knn_launch<8>(a);
+        else knn_launch<16>(a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(count, d_count, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, 0));
+        if (index) HIP_TRY(hipMemcpyAsync(index, d_index, sizeof(int32_t) * n_q * k, hipMemcpyDeviceToHost, 0));
+        HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 2 * n_q, hipMemcpyDeviceToHost));   // (synchronous: the host arrays are the caller's)
+        HIP_TRY(hipStreamSynchronize(0));
+    }
+    if (index && !map.empty())                                          // compacted indices -> the caller's
+        for (int64_t e = 0; e < n_q * k; ++e) if (index[e] >= 0) index[e] = map[index[e]];
+done:
+    if (device != -1) (void)hipSetDevice(prev);
     return rc;
 }

@@ -218,13 +218,41 @@ def _triangulation(src):
     return Delaunay(src)
 
 
-def interpolation_near(x1, y1, x2, y2, x1grd, y1grd, method='linear', first_guess_device=None, **kwargs):
+def interpolation_near(x1, y1, x2, y2, x1grd, y1grd, method='linear', first_guess_device=None, knn_k=5, knn_max_dist=None,
+                       knn_displacement=True, **kwargs):
     """scipy griddata of x2/y2 from the keypoints onto the grid points; NaN outside the
     convex hull (reference lib.py:179-201; note the (row, col) point order).
 
     ``first_guess_device`` (not a reference argument): GPU index on which the grid points are located in the
     triangulation and interpolated (include/sid_fg.h) - the triangulation is SciPy's Delaunay either way.  ``None``
-    evaluates with SciPy on the host."""
+    evaluates with SciPy on the host.
+
+    ``method='knn'`` with ``knn_k`` (1..16, default 5) and ``knn_max_dist`` (pixels; None: no limit) - none of them the
+    reference's: the component-wise median of x2 / y2 over the ``knn_k`` nearest key points (include/sid_fg.h sid_fg_knn,
+    DESIGN.md section 20).  No triangulation and no SciPy call: the search runs on ``first_guess_device``, or in the
+    library's host instance when that is None - the same numbers bit for bit.  Defined everywhere (no convex hull); NaN
+    only where ``knn_max_dist`` leaves a grid point without a key point.  A median ignores up to (knn_k - 1) / 2 wrong
+    key points around a grid point, which a linear interpolant passes on into every triangle they touch.  Key-point
+    values that are not finite raise ValueError.  ``knn_displacement=True`` (default): x2, y2 are positions, as in the
+    first guess - the median is taken over the key points' displacements x2 - x1, y2 - y1 and added to the grid point
+    (the median of the neighbours' positions would be the position of one neighbour, tens of pixels from the grid
+    point: a linear interpolant reproduces a shift either way, a median only this way).  False: x2, y2 are the values
+    of a field and their median is the result (the residuals of ``old_border=False``)."""
+    if method == 'knn':
+        from . import _capi
+        vals = np.array([x2, y2], dtype=np.float64).T
+        if not np.isfinite(vals).all():
+            raise ValueError("method='knn': key-point values (x2, y2) must be finite")
+        src = np.array([y1, x1], dtype=np.float64).T
+        grd_shape = np.shape(x1grd)
+        flat = np.array([np.ravel(y1grd), np.ravel(x1grd)], dtype=np.float64).T
+        if knn_displacement:
+            vals = vals - src[:, ::-1]
+        both = _capi.fg_knn(src, vals, flat, k=knn_k, max_dist=knn_max_dist,
+                            device=-1 if first_guess_device is None else first_guess_device)
+        if knn_displacement:
+            both = flat[:, ::-1] + both
+        return both[:, 0].reshape(grd_shape), both[:, 1].reshape(grd_shape)
     src = np.array([y1, x1]).T
     dst = np.array([y1grd, x1grd]).T
     if method == 'linear' and src.shape[1] == 2:

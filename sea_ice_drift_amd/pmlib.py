@@ -123,8 +123,11 @@ def prepare_first_guess(c2pm1, r2pm1, n1, c1, r1, n2, c2, r2, img_size,
         border[inside] = nearest_keypoint_distance(c2, r2, rq, cq, shape=n2_shape, device=fg_dev)
     else:
         c2t, r2t = interpolation_poly(c1n2, r1n2, c2, r2, c1n2, r1n2, **kwargs)
-        # (these values are not rounded but go through hypot and floor: SciPy's own evaluation, so that no last bit differs)
-        c2d, r2d = interpolation_near(c1n2, r1n2, c2 - c2t, r2 - r2t, c2pm1, r2pm1, first_guess_device=None, **kwargs)
+        # (these values are not rounded but go through hypot and floor: SciPy's own evaluation, so that no last bit differs;
+        # method='knn' has one specification on the device and on the host, include/sid_fg.h, and stays where it was)
+        res_dev = fg_dev if kwargs.get('method') == 'knn' else None
+        c2d, r2d = interpolation_near(c1n2, r1n2, c2 - c2t, r2 - r2t, c2pm1, r2pm1, first_guess_device=res_dev,
+                                      **dict(kwargs, knn_displacement=False))          # (residuals: a field's values, not positions)
         border = np.hypot(c2d, r2d)
 
     border[border < min_border] = min_border
@@ -596,6 +599,11 @@ def pattern_matching(lon_pm1, lat_pm1, n1, c1, r1, n2, c2, r2,
         of its arithmetic and evaluates exactly those with SciPy itself (lib.interpolation_near; fixture G4 pins the
         prelude with both paths, tests/test_gpu_first_guess.py the flagging).  A triangulation with a degenerate simplex
         and ``old_border=False`` (unrounded values) are evaluated by SciPy alone.
+    ``method`` = 'linear' (default, the reference's) | 'nearest' | 'cubic' | 'knn', with ``knn_k`` = 5 and ``knn_max_dist`` =
+        None - 'knn' and its two knobs are not the reference's: the first guess is the median of the ``knn_k`` nearest key
+        points, found on the GPU without a triangulation (``lib.interpolation_near``).  It is robust
+        to wrong key points and takes Qhull out of the call; a grid point that ``knn_max_dist`` leaves without a key point
+        gets the polynomial first guess and ``max_border``, like a point outside the hull with 'linear'.
     ``device`` (GPU index, default 0) and ``context`` (a ``_capi.PMContext`` of the caller's, for two calls in flight on
         one GPU).
     ``devices`` = None (default: the one handle of ``device``) | 'all' | a count | a sequence of GPU indices, e.g.

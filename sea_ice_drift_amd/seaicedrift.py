@@ -15,9 +15,12 @@ from sea_ice_drift_amd.pmlib import pattern_matching
 class SeaIceDrift(object):
     """Retrieve sea ice drift with pattern matching on an MI355X."""
 
-    def __init__(self, n1, n2, devices=None, **kwargs):
+    def __init__(self, n1, n2, devices=None, first_guess_method=None, **kwargs):
         """``devices``: the GPUs that ``get_drift_FT`` and ``get_drift_PM`` use unless a call names its own - None (one
-        handle, GPU ``device=`` of the call), 'all', a count or a sequence of GPU indices (``pmlib.resolve_devices``)."""
+        handle, GPU ``device=`` of the call), 'all', a count or a sequence of GPU indices (``pmlib.resolve_devices``).
+        ``first_guess_method`` (not the reference's): the ``method=`` of ``get_drift_PM`` unless a call names its own - None
+        (the reference's 'linear') or e.g. 'knn', the triangulation-free first guess of ``lib.interpolation_near``; with
+        'knn' ``get_drift_FT`` starts no triangulation ahead of ``get_drift_PM``."""
         for n in (n1, n2):
             if isinstance(n, str):
                 raise NotImplementedError(
@@ -27,6 +30,7 @@ class SeaIceDrift(object):
         self.n1 = n1
         self.n2 = n2
         self.devices = devices
+        self.first_guess_method = first_guess_method
 
     def get_drift_FT(self, **kwargs):
         """Same returns as the reference (seaicedrift.py:42-60): u, v, lon1, lat1, lon2, lat2 of the matched
@@ -54,6 +58,8 @@ class SeaIceDrift(object):
             import numpy as np
             if len(lon1) < 4 or os.environ.get('SID_NO_TRI_PREFETCH'):   # (the switch: A/B runs)
                 return
+            if self.first_guess_method == 'knn':                         # (that first guess has no triangulation)
+                return
             x1, y1 = self.n1.transform_points(lon1, lat1, 1)             # get_drift_PM (seaicedrift.py:85)
             lon, lat = self.n1.transform_points(x1, y1)                  # prepare_first_guess (pmlib.py:280-282)
             c1n2, r1n2 = self.n2.transform_points(lon, lat, 1)
@@ -70,6 +76,8 @@ class SeaIceDrift(object):
         drift with the parabolic sub-pixel offset of the correlation peak, what ``libdefor`` wants to be fed."""
         if self.devices is not None:
             kwargs.setdefault('devices', self.devices)
+        if self.first_guess_method is not None:
+            kwargs.setdefault('method', self.first_guess_method)
         x1, y1 = self.n1.transform_points(lon1, lat1, 1)
         x2, y2 = self.n2.transform_points(lon2, lat2, 1)
         return pattern_matching(lons, lats, self.n1, x1, y1, self.n2, x2, y2, **kwargs)
