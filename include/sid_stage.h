@@ -62,6 +62,29 @@ int sid_stage_order_stats(const float *d_img, int64_t rows, int64_t cols, int64_
 int sid_stage_scale_u8(const float *d_img, int64_t rows, int64_t cols, int64_t stride, float vmin, float denom,
                        uint8_t *d_out, int64_t out_stride, void *hip_stream);
 
+/* Test support: which route the order statistics took.  Fills *out from what the workspace's host side remembers; launches
+ * nothing, waits for nothing, changes no result.  The first group is what the last sid_stage_begin / sid_stage_begin_hint kept
+ * (n_hint = 0 and all ranges zero after a plain begin), the second what the last sid_stage_order_stats_ws did (zero before
+ * the first call after a begin).
+ *   lo, span, shift  the sampled key range q: keys lo .. lo + span, bins of 2^shift keys (a range that matches no key:
+ *                    lo = 0xffffffff, span = 0);  below, inside: non-NaN pixels with a key below / inside it
+ *   m_valid          non-NaN pixels among the sampled ones (fewer than 256: no range was formed)
+ *   n_direct         ranks answered from the begin's histogram alone (shift 0: a bin is one key)
+ *   n_resolved       ranks answered by a resolving pass over their bin;  resolve_passes: such passes launched,
+ *                    resolve_states: key ranges of up to 2048 keys they carried in total (ranks in one bin share theirs)
+ *   n_radix          ranks that took the three-pass radix select
+ *   image_passes     kernel passes over the whole image since and including the last begin (the sampler reads 8192 pixels
+ *                    and is not one). */
+typedef struct sid_stage_route {
+    int64_t  n_valid;
+    int64_t  below[4], inside[4];
+    uint32_t lo[4], span[4], shift[4];
+    uint32_t m_valid;
+    int32_t  n_hint;
+    int32_t  n_direct, n_resolved, n_radix, resolve_passes, resolve_states, image_passes;
+} sid_stage_route;
+int sid_stage_debug_route(const sid_stage_ws *ws, sid_stage_route *out);
+
 const char *sid_stage_last_error(void);
 
 #ifdef __cplusplus

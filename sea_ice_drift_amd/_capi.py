@@ -34,7 +34,8 @@ FT_SYMBOLS = ('sid_ft_knn2', 'sid_ft_knn2_device', 'sid_ft_workspace_bytes', 'si
 
 # every symbol include/sid_stage.h declares (uint8 staging, same library)
 STAGE_SYMBOLS = ('sid_stage_create', 'sid_stage_destroy', 'sid_stage_begin', 'sid_stage_begin_hint', 'sid_stage_order_stats_ws',
-                 'sid_stage_count_valid', 'sid_stage_order_stats', 'sid_stage_scale_u8', 'sid_stage_last_error')
+                 'sid_stage_count_valid', 'sid_stage_order_stats', 'sid_stage_scale_u8', 'sid_stage_debug_route',
+                 'sid_stage_last_error')
 
 # every symbol include/sid_orb.h declares (key-point detector, same library)
 ORB_SYMBOLS = ('sid_orb_detect', 'sid_orb_last_error', 'sid_orb_release')
@@ -150,6 +151,8 @@ def lib():
     if hasattr(L, 'sid_stage_begin_hint'):
         L.sid_stage_begin_hint.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_int,
                                            C.POINTER(C.c_int64), C.c_void_p]
+    if hasattr(L, 'sid_stage_debug_route'):      # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        L.sid_stage_debug_route.argtypes = [C.c_void_p, C.c_void_p]
     L.sid_orb_detect.argtypes = [C.c_int, _u8p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int8), _i32p,
                                  _f32p, _i32p, C.POINTER(C.c_int64), _u8p, C.c_int64, C.POINTER(C.c_int64)]
     L.sid_orb_last_error.restype = C.c_char_p
@@ -630,6 +633,15 @@ def _stage_check(rc):
         raise SidPmError(rc, lib().sid_stage_last_error().decode())
 
 
+class _StageRoute(C.Structure):
+    """struct sid_stage_route (include/sid_stage.h)."""
+    _fields_ = [('n_valid', C.c_int64), ('below', C.c_int64 * 4), ('inside', C.c_int64 * 4),
+                ('lo', C.c_uint32 * 4), ('span', C.c_uint32 * 4), ('shift', C.c_uint32 * 4),
+                ('m_valid', C.c_uint32), ('n_hint', C.c_int32),
+                ('n_direct', C.c_int32), ('n_resolved', C.c_int32), ('n_radix', C.c_int32),
+                ('resolve_passes', C.c_int32), ('resolve_states', C.c_int32), ('image_passes', C.c_int32)]
+
+
 class StageWorkspace(object):
     """Persistent device + pinned host buffers of the staging step (include/sid_stage.h sid_stage_create)."""
 
@@ -666,6 +678,16 @@ class StageWorkspace(object):
         out = np.empty(len(r), dtype=np.float32)
         _stage_check(lib().sid_stage_order_stats_ws(self._h, r.ctypes.data_as(C.POINTER(C.c_int64)), len(r), out.ctypes.data_as(_f32p)))
         return out
+
+    def route(self):
+        """Which route the last begin / order_stats took (include/sid_stage.h sid_stage_debug_route; test support): a dict of
+        the struct's fields, the per-range ones as lists of n_hint Python ints."""
+        s = _StageRoute()
+        _stage_check(lib().sid_stage_debug_route(self._h, C.byref(s)))
+        d = {name: int(getattr(s, name)) for name, kind in _StageRoute._fields_ if not hasattr(kind, '_length_')}
+        for name in ('lo', 'span', 'shift', 'below', 'inside'):
+            d[name] = [int(v) for v in getattr(s, name)[:d['n_hint']]]
+        return d
 
 
 def stage_count_valid(ptr, rows, cols, stride, stream=0):

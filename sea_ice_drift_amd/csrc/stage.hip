@@ -395,12 +395,17 @@ struct sid_stage_ws {
     unsigned long long *d_counts = nullptr, *h_counts = nullptr;     // [1 + kMaxStates]
     int n_hint = 0;
     uint32_t hint_lo[kMaxHint], hint_shift[kMaxHint];
+    uint32_t hint_span[kMaxHint], hint_m = 0;                        // (sid_stage_debug_route: h_states is reused by the resolving passes)
     unsigned long long hint_below[kMaxHint], hint_inside[kMaxHint];
     std::vector<unsigned long long> hint_hist;                       // [n_hint][kBins]
     unsigned long long n_valid = 0;
     const float *img = nullptr; int64_t rows = 0, cols = 0, stride = 0;
     hipStream_t stream = nullptr;
     bool have = false;
+    // what sid_stage_debug_route reports: host counters only
+    int passes = 0;                                                  // kernel passes over the image since the last begin
+    int n_direct = 0, n_resolved = 0, n_radix = 0, resolve_passes = 0, resolve_states = 0;   // of the last order_stats_ws
+    void begin_route() { passes = 0; n_direct = n_resolved = n_radix = resolve_passes = resolve_states = 0; hint_m = 0; }
 };
 
 namespace {
@@ -430,6 +435,7 @@ int run_hist(sid_stage_ws *ws, const HistStates &S, uint32_t mask, int shift, in
         else if (vec) hipLaunchKernelGGL((hist_kernel<false, true>), grid, block, lds, st, ws->img, ws->rows, ws->cols, ws->stride, S, mask, shift, nbins, ws->d_hist);
         else hipLaunchKernelGGL((hist_kernel<false, false>), grid, block, lds, st, ws->img, ws->rows, ws->cols, ws->stride, S, mask, shift, nbins, ws->d_hist);
         e = hipGetLastError();
+        ++ws->passes;
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ws->h_hist, ws->d_hist, bytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -467,6 +473,7 @@ int run_range(sid_stage_ws *ws, int n_states, bool count)
     else { if (nq == 1) SID_RANGE(1, false); else if (nq == 2) SID_RANGE(2, false); else if (nq == 4) SID_RANGE(4, false); else SID_RANGE(8, false); }
 #undef SID_RANGE
     HIP_TRY(hipGetLastError());
+    ++ws->passes;
     HIP_TRY(hipMemcpyAsync(ws->h_hist, ws->d_hist, (size_t)n_states * kBins * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     if (count) HIP_TRY(hipMemcpyAsync(ws->h_counts, ws->d_counts, (1 + kMaxStates) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     else HIP_TRY(hipStreamSynchronize(st));
@@ -527,6 +534,7 @@ SID_EXPORT int sid_stage_begin(sid_stage_ws *ws, const float *d_img, int64_t row
     }
     ws->img = d_img; ws->rows = rows; ws->cols = cols; ws->stride = stride; ws->stream = reinterpret_cast<hipStream_t>(hip_stream);
     ws->have = false; ws->n_hint = 0;
+    ws->begin_route();
     if (int rc = first_digit_pass(ws)) return rc;
     ws->have = true;
     *n_valid = (int64_t)ws->n_valid;
@@ -549,6 +557,7 @@ SID_EXPORT int sid_stage_begin_hint(sid_stage_ws *ws, const float *d_img, int64_
     }
     ws->img = d_img; ws->rows = rows; ws->cols = cols; ws->stride = stride; ws->stream = reinterpret_cast<hipStream_t>(hip_stream);
     ws->have = false; ws->have_first = false; ws->n_hint = 0;
+    ws->begin_route();
     hipStream_t st = ws->stream;
     HintIn H; H.n = n_fractions;
     for (int q = 0; q < kMaxHint; ++q) H.frac[q] = q < n_fractions ? fractions[q] : 0.0;
@@ -560,12 +569,13 @@ SID_EXPORT int sid_stage_begin_hint(sid_stage_ws *ws, const float *d_img, int64_
     ws->n_valid = ws->h_counts[0];
     ws->hint_hist.assign(ws->h_hist, ws->h_hist + (size_t)n_fractions * kBins);
     for (int q = 0; q < n_fractions; ++q) {
-        ws->hint_lo[q] = ws->h_states->lo[q]; ws->hint_shift[q] = ws->h_states->shift[q];
+        ws->hint_lo[q] = ws->h_states->lo[q]; ws->hint_shift[q] = ws->h_states->shift[q]; ws->hint_span[q] = ws->h_states->span[q];
         ws->hint_below[q] = ws->h_counts[1 + q];
         unsigned long long in = 0;
         for (int b = 0; b < kBins; ++b) in += ws->hint_hist[(size_t)q * kBins + b];
         ws->hint_inside[q] = in;
     }
+    ws->hint_m = ws->h_states->m_valid;
     ws->n_hint = n_fractions;
     ws->have = true;
     *n_valid = (int64_t)ws->n_valid;
@@ -578,6 +588,7 @@ SID_EXPORT int sid_stage_order_stats_ws(sid_stage_ws *ws, const int64_t *ranks, 
     if (n_ranks < 0 || (n_ranks > 0 && (!ranks || !values))) return fail(SID_PM_ERR_ARG, "bad rank list");
     for (int q = 0; q < n_ranks; ++q) if (ranks[q] < 0) return fail(SID_PM_ERR_ARG, "negative rank");
     DeviceGuard guard(ws->device);
+    ws->n_direct = ws->n_resolved = ws->n_radix = ws->resolve_passes = ws->resolve_states = 0;
     // ---- ranks inside a hinted range (sid_stage_begin_hint): the bin is known, one more pass resolves it to a key ----
     std::vector<int64_t> slow_ranks; std::vector<int> slow_at;
     {
@@ -594,26 +605,29 @@ SID_EXPORT int sid_stage_order_stats_ws(sid_stage_ws *ws, const int64_t *ranks, 
                 int b = 0;
                 while (r >= hq[b]) { r -= hq[b]; ++b; }
                 const uint32_t base = ws->hint_lo[q] + ((uint32_t)b << ws->hint_shift[q]);
-                if (ws->hint_shift[q] == 0u) values[k] = key2f(base);       // a bin is one key
-                else wants.push_back(Want{k, base, 1u << ws->hint_shift[q], r, -1});
+                if (ws->hint_shift[q] == 0u) { values[k] = key2f(base); ++ws->n_direct; }   // a bin is one key
+                else { wants.push_back(Want{k, base, 1u << ws->hint_shift[q], r, -1}); ++ws->n_resolved; }
                 done = true;
             }
-            if (!done) { slow_ranks.push_back(ranks[k]); slow_at.push_back(k); }
+            if (!done) { slow_ranks.push_back(ranks[k]); slow_at.push_back(k); ++ws->n_radix; }
         }
         for (size_t w0 = 0; w0 < wants.size();) {                          // up to kMaxStates pieces of 2048 keys per pass
             RangeStates &S = *ws->h_states;
             int ns = 0;
+            uint32_t owner[kMaxStates];                                    // width of the bin whose first piece a state is (0: a later piece)
             size_t w1 = w0;
             for (; w1 < wants.size(); ++w1) {                              // a bin wider than 2048 keys takes consecutive states
                 const int pieces = (int)std::max<uint32_t>(1u, wants[w1].width >> 11);
                 int f = -1;
-                for (int t = 0; t < ns; ++t) if (S.lo[t] == wants[w1].base) f = t;
+                // (the same bin: base AND width - bins of two overlapping ranges can start at one key with different widths)
+                for (int t = 0; t < ns; ++t) if (S.lo[t] == wants[w1].base && owner[t] == wants[w1].width) f = t;
                 if (f < 0) {
                     if (ns + pieces > kMaxStates) break;
                     f = ns;
                     for (int pc = 0; pc < pieces; ++pc, ++ns) {
                         S.lo[ns] = wants[w1].base + ((uint32_t)pc << 11);
                         S.span[ns] = std::min<uint32_t>(wants[w1].width, 2048u) - 1u; S.shift[ns] = 0u;
+                        owner[ns] = pc == 0 ? wants[w1].width : 0u;
                     }
                 }
                 wants[w1].state = f;
@@ -621,6 +635,7 @@ SID_EXPORT int sid_stage_order_stats_ws(sid_stage_ws *ws, const int64_t *ranks, 
             for (int t = ns; t < kMaxStates; ++t) { S.lo[t] = 0xffffffffu; S.span[t] = 0u; S.shift[t] = 0u; }
             HIP_TRY(hipMemcpyAsync(ws->d_states, ws->h_states, sizeof(RangeStates), hipMemcpyHostToDevice, ws->stream));
             if (int rc = run_range(ws, ns, false)) return rc;
+            ++ws->resolve_passes; ws->resolve_states += ns;
             for (size_t w = w0; w < w1; ++w) {
                 // (the states of one bin are consecutive rows of the histogram: bins 0 .. 2047 of each, in key order)
                 const unsigned long long *hq = ws->h_hist + (size_t)wants[w].state * kBins;
@@ -680,6 +695,23 @@ int radix_select(sid_stage_ws *ws, const int64_t *ranks, int n_ranks, float *val
     return SID_PM_OK;
 }
 }  // namespace
+
+// test support: the route of the last begin / order_stats_ws, from the host's own counters (no launch, no wait)
+SID_EXPORT int sid_stage_debug_route(const sid_stage_ws *ws, sid_stage_route *out)
+{
+    if (!ws || !out) return fail(SID_PM_ERR_ARG, "null workspace or output");
+    if (!ws->have) return fail(SID_PM_ERR_STATE, "debug_route needs sid_stage_begin on an image first");
+    memset(out, 0, sizeof *out);
+    out->n_valid = (int64_t)ws->n_valid;
+    out->n_hint = ws->n_hint; out->m_valid = ws->hint_m;
+    for (int q = 0; q < ws->n_hint; ++q) {
+        out->lo[q] = ws->hint_lo[q]; out->span[q] = ws->hint_span[q]; out->shift[q] = ws->hint_shift[q];
+        out->below[q] = (int64_t)ws->hint_below[q]; out->inside[q] = (int64_t)ws->hint_inside[q];
+    }
+    out->n_direct = ws->n_direct; out->n_resolved = ws->n_resolved; out->n_radix = ws->n_radix;
+    out->resolve_passes = ws->resolve_passes; out->resolve_states = ws->resolve_states; out->image_passes = ws->passes;
+    return SID_PM_OK;
+}
 
 // one-shot forms (a temporary workspace per call)
 SID_EXPORT int sid_stage_count_valid(const float *d_img, int64_t rows, int64_t cols, int64_t stride, int64_t *n_valid,

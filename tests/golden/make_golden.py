@@ -32,10 +32,13 @@ them, with a sha256) and the outputs the reference's functions returned:
                      subsample of the 200x200 grid (regression pin, not reference output)
   g6_uint8_image.npz lib.get_uint8_image             (lib.py:27-59) on seeded float32 images with NaN / inf
                      pixels, percentile-driven and explicit vmin / vmax
+  g6b_uint8_small.npz  lib.get_uint8_image on the small sampler and key-space cases of tests/stage_cases.py (sizes around
+                     the staging sampler's 8192 pixels, +-inf, signed zeros, subnormals, +-FLT_MAX, NaN payloads), four
+                     percentile pairs, as sha256 + a subsample; the outputs whose float result holds a NaN (its uint8 cast is undefined in C) by name only
   g7_feature_tracking.npz  ftlib.feature_tracking    (ftlib.py:241-285: domain, Lowe, drift and least-squares
                      filters) on synthetic key points / descriptors, brute-force matcher injected
 
-    python tests/golden/make_golden.py [g1 g2 g3 g4 g5 ... g9]
+    python tests/golden/make_golden.py [g1 g2 g3 g4 g5 g6 g6b ... g9]
 """
 import os
 import sys
@@ -513,6 +516,37 @@ def make_g6(reflib):
     np.savez_compressed(os.path.join(HERE, 'g6_uint8_image.npz'), **d)
 
 
+def make_g6b(reflib):
+    """lib.get_uint8_image (lib.py:27-59) run as the reference wrote it on the small cases of tests/stage_cases.py that have at
+    least two distinct finite values.  A result whose float image holds a NaN at a finite pixel (vmin == vmax, an infinite
+    percentile, an overflow) is not stored: the cast of NaN to uint8 is undefined in C; its key goes to 'left_to_the_oracle'."""
+    import contextlib, io
+    from tests import stage_cases
+    names, shas, vmins, vmaxs, subs, left = [], [], [], [], [], []
+    for name, img in sorted(stage_cases.public_cases().items()):
+        if not stage_cases.has_two_finite_values(img):
+            continue
+        for pi, (pmin, pmax) in enumerate(stage_cases.PERCENTILE_PAIRS):
+            with np.errstate(all='ignore'):
+                vmin, vmax = np.nanpercentile(img, pmin), np.nanpercentile(img, pmax)
+                u = 1 + 254 * (img - vmin) / (vmax - vmin)
+            if np.isnan(u[np.isfinite(img)]).any():
+                left.append('out_%s_%d' % (name, pi))
+                continue
+            with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
+                out = reflib.get_uint8_image(img.copy(), None, None, pmin, pmax)
+            assert out.dtype == np.uint8 and out.shape == img.shape
+            names.append('out_%s_%d' % (name, pi))
+            shas.append(syn.sha256(out))
+            subs.append(out.ravel()[::stage_cases.G6B_EVERY])
+            vmins.append(np.float64(vmin))
+            vmaxs.append(np.float64(vmax))
+    # one array per kind (a member per output would cost more in zip headers than in numbers): output k is names[k]
+    np.savez_compressed(os.path.join(HERE, 'g6b_uint8_small.npz'), numpy_version=np.__version__, names=np.array(names),
+                        sha=np.array(shas), vmin=np.array(vmins), vmax=np.array(vmaxs), sub=np.concatenate(subs),
+                        sub_start=np.cumsum([0] + [len(s) for s in subs]), left_to_the_oracle=np.array(left))
+
+
 class G7KeyPoint(object):
     """What the reference reads of a cv2.KeyPoint."""
     def __init__(self, x, y):
@@ -604,7 +638,7 @@ def make_g7():
 
 
 def main():
-    which = sys.argv[1:] or ['g1', 'g1b', 'g1c', 'g2', 'g3', 'g3b', 'g3c', 'g3d', 'g4', 'g5', 'g6', 'g7', 'g8', 'g9']
+    which = sys.argv[1:] or ['g1', 'g1b', 'g1c', 'g2', 'g3', 'g3b', 'g3c', 'g3d', 'g4', 'g5', 'g6', 'g6b', 'g7', 'g8', 'g9']
     if 'g7' in which:
         t = time.time()
         make_g7()
@@ -614,6 +648,10 @@ def main():
         t = time.time()
         make_g6(reflib)
         print('g6 done in %.1f s' % (time.time() - t))
+    if 'g6b' in which:
+        t = time.time()
+        make_g6b(reflib)
+        print('g6b done in %.1f s' % (time.time() - t))
     c_oracle.build()
     for name, fn in (('g1', make_g1), ('g1b', make_g1b), ('g1c', make_g1c), ('g3d', make_g3d), ('g2', make_g2), ('g3', make_g3), ('g3b', make_g3b), ('g3c', make_g3c), ('g4', make_g4), ('g8', make_g8), ('g9', make_g9)):
         if name in which:
