@@ -52,6 +52,11 @@ GRID_SYMBOLS = ('sid_grid_filter', 'sid_grid_deformation', 'sid_grid_filter_devi
                 'sid_grid_last_error', 'sid_grid_release')
 GRID_DIAGONALS = {'shorter': 0, 'main': 1, 'anti': 2}     # SID_GRID_DIAG_*
 GRID_TILE = (8, 32)                                       # SID_GRID_TILE_ROWS, SID_GRID_TILE_COLS: the filter kernel's tile
+# include/sid_warp.h: piecewise-affine warp of an image along a drift grid
+WARP_SYMBOLS = ('sid_warp_image', 'sid_warp_image_device', 'sid_warp_last_error', 'sid_warp_release')
+WARP_DTYPES = {'uint8': 0, 'float32': 1}                  # SID_WARP_U8, SID_WARP_F32
+WARP_KEEP_ZERO = 1                                        # SID_WARP_KEEP_ZERO
+WARP_TILE = (16, 64)                                      # SID_WARP_TILE_ROWS, SID_WARP_TILE_COLS: one work item of the warp kernel
 
 # every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
 PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
@@ -181,6 +186,14 @@ def lib():
         L.sid_grid_deformation_device.argtypes = [vp] * 5 + [C.c_int64, C.c_int64, C.c_int] + [vp] * 7
         L.sid_grid_last_error.restype = C.c_char_p
         L.sid_grid_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_warp_image'):
+        vp = C.c_void_p
+        tail = [C.c_int64, C.c_int64, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double,
+                C.c_int, C.c_uint32, vp, C.c_int64, vp, vp, vp]
+        L.sid_warp_image.argtypes = [C.c_int] + [_f64p] * 4 + [_u8p] + tail
+        L.sid_warp_image_device.argtypes = [vp] * 5 + tail + [vp]
+        L.sid_warp_last_error.restype = C.c_char_p
+        L.sid_warp_release.argtypes = [C.c_int]
     if hasattr(L, 'sid_prep_apply'):
         vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
         L.sid_prep_subsample.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, C.c_int64, vp, vp]
@@ -239,14 +252,14 @@ def _p(a, t):
 
 def release_workspaces(device=-1):
     """Hand the cached device memory of the detector, the matcher, the first-guess evaluation and the deformation back
-    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``; -1: every device).  No call on that device may be in flight.
+    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``; -1: every device).  No call on that device may be in flight.
     A process that never loaded the library has nothing cached: this returns without loading it (it is registered with
     atexit through pmlib.release_contexts, and loading means importing torch and initialising the GPU - not at interpreter
     shutdown, and not in a process that only used the host code)."""
     if _lib is None:
         return
     L = _lib
-    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release'):
+    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release', 'sid_warp_release'):
         if hasattr(L, name):
             getattr(L, name)(int(device))
 
@@ -866,6 +879,44 @@ def grid_deformation_device(x, y, u, v, valid, rows, cols, diagonal, outs, strea
     """``sid_grid_deformation_device`` on raw device pointers: outs = (e1, e2, e3, a, p, t)."""
     _grid_check(lib().sid_grid_deformation_device(*[C.c_void_p(int(q)) for q in (x, y, u, v, valid)], int(rows), int(cols),
                                                   int(diagonal), *[C.c_void_p(int(q)) for q in outs], C.c_void_p(int(stream))))
+
+
+def _warp_check(rc):
+    if rc != 0:
+        raise SidPmError(rc, lib().sid_warp_last_error().decode())
+
+
+def _vp_of(a):
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def warp_image(x, y, xs, ys, valid, src, dtype, src_shape, out_shape, order, fill, diagonal, flags, want_out, want_covered,
+               want_maps, device=0):
+    """``sid_warp_image`` on host arrays: x, y, xs, ys float64 [R, C] and valid uint8 or None (C-contiguous); src a 2-D
+    array of `dtype` ('uint8' or 'float32') with unit inner stride, or None; -> out, covered, map_x, map_y (None where not
+    wanted).  device=-1: the kernels' source in a host loop (tests)."""
+    rows, cols = x.shape
+    ro, co = int(out_shape[0]), int(out_shape[1])
+    out = np.empty((ro, co), dtype=dtype) if want_out else None
+    covered = np.empty((ro, co), dtype=np.uint8) if want_covered else None
+    map_x = np.empty((ro, co), dtype=np.float32) if want_maps else None
+    map_y = np.empty((ro, co), dtype=np.float32) if want_maps else None
+    stride = src.strides[0] // src.itemsize if src is not None and src.shape[0] > 1 else int(src_shape[1])
+    _warp_check(lib().sid_warp_image(int(device), *[_p(a, _f64p) for a in (x, y, xs, ys)], _opt_u8(valid), rows, cols,
+                                     _vp_of(src), WARP_DTYPES[dtype], int(src_shape[0]), int(src_shape[1]), stride, ro, co,
+                                     int(order), float(fill), int(diagonal), int(flags), _vp_of(out), co, _vp_of(covered),
+                                     _vp_of(map_x), _vp_of(map_y)))
+    return out, covered, map_x, map_y
+
+
+def warp_image_device(x, y, xs, ys, valid, rows, cols, src, dtype, src_shape, src_stride, out_shape, order, fill, diagonal,
+                      flags, out, out_stride, covered, map_x, map_y, stream):
+    """``sid_warp_image_device`` on raw device pointers (torch ``data_ptr()``; 0 for none)."""
+    vp = [C.c_void_p(int(q)) if q else None for q in (x, y, xs, ys, valid, src, out, covered, map_x, map_y)]
+    _warp_check(lib().sid_warp_image_device(*vp[:5], int(rows), int(cols), vp[5], WARP_DTYPES[dtype], int(src_shape[0]),
+                                            int(src_shape[1]), int(src_stride), int(out_shape[0]), int(out_shape[1]),
+                                            int(order), float(fill), int(diagonal), int(flags), vp[6], int(out_stride),
+                                            vp[7], vp[8], vp[9], C.c_void_p(int(stream))))
 
 
 def _prep_check(rc):

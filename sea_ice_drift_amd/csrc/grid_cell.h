@@ -16,14 +16,13 @@ enum { kShorter = 0, kMain = 1, kAnti = 2 };          // SID_GRID_DIAG_* of sid_
 // q[k] for a run-time k in 0..3 without indexing an array by it (that would put the array into scratch on the device)
 SID_HD_INLINE double pick(const double q[4], int k) { return k == 0 ? q[0] : k == 1 ? q[1] : k == 2 ? q[2] : q[3]; }
 
-// One grid cell.  Ring nodes 0..3 = A, B, E, D (A = (i, j), B = (i, j + 1), E = (i + 1, j + 1), D = (i + 1, j)); bit k of
-// `usable` is set when ring node k is usable; x, y, u, v hold the four nodes in ring order (anything where not usable: never
-// read into a result).  `ids` are the flat node numbers of the ring.  Writes slot s = 0, 1 to out[5][2] (e1, e2, e3, a, p)
-// and t[2][3]: NaN and -1 where the slot holds no triangle.
-SID_HD_INLINE void cell(const double x[4], const double y[4], const double u[4], const double v[4], unsigned usable, int diagonal,
-                        const int32_t ids[4], double out[5][2], int32_t t[2][3])
+// The triangle slots of one grid cell, before orientation.  Ring nodes 0..3 = A, B, E, D (A = (i, j), B = (i, j + 1),
+// E = (i + 1, j + 1), D = (i + 1, j)); bit k of `usable` is set when ring node k is usable; x, y hold the four nodes in ring
+// order.  Slot s is the ring nodes (ta[s], tb[s], tc[s]), or ta[s] = -1 when it holds no triangle.  (Also the cells of
+// warp_pixel.h.)
+SID_HD_INLINE void split(const double x[4], const double y[4], unsigned usable, int diagonal, int ta[2], int tb[2], int tc[2])
 {
-    int ta[2] = {-1, -1}, tb[2] = {-1, -1}, tc[2] = {-1, -1};
+    ta[0] = ta[1] = tb[0] = tb[1] = tc[0] = tc[1] = -1;
     const int n = (int)(usable & 1) + (int)((usable >> 1) & 1) + (int)((usable >> 2) & 1) + (int)((usable >> 3) & 1);
     if (n == 4) {
         const double mx = x[2] - x[0], my = y[2] - y[0], ax = x[3] - x[1], ay = y[3] - y[1];
@@ -35,6 +34,16 @@ SID_HD_INLINE void cell(const double x[4], const double y[4], const double u[4],
         const int gone = !(usable & 1) ? 0 : !(usable & 2) ? 1 : !(usable & 4) ? 2 : 3;
         ta[0] = gone == 0 ? 1 : 0; tb[0] = gone <= 1 ? 2 : 1; tc[0] = gone == 3 ? 2 : 3;
     }
+}
+
+// One grid cell: x, y, u, v hold the four nodes in ring order (anything where not usable: never read into a result).  `ids`
+// are the flat node numbers of the ring.  Writes slot s = 0, 1 to out[5][2] (e1, e2, e3, a, p) and t[2][3]: NaN and -1 where
+// the slot holds no triangle.
+SID_HD_INLINE void cell(const double x[4], const double y[4], const double u[4], const double v[4], unsigned usable, int diagonal,
+                        const int32_t ids[4], double out[5][2], int32_t t[2][3])
+{
+    int ta[2], tb[2], tc[2];
+    split(x, y, usable, diagonal, ta, tb, tc);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         if (ta[s] < 0) {

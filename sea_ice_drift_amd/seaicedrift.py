@@ -9,6 +9,7 @@ is outside the scope of this package - passing file names raises with a pointer 
 """
 from sea_ice_drift_amd.ftlib import feature_tracking
 from sea_ice_drift_amd.lib import get_drift_vectors, prefetch_triangulation
+from sea_ice_drift_amd.libwarp import warp_image
 from sea_ice_drift_amd.pmlib import pattern_matching
 
 
@@ -81,3 +82,26 @@ class SeaIceDrift(object):
         x1, y1 = self.n1.transform_points(lon1, lat1, 1)
         x2, y2 = self.n2.transform_points(lon2, lat2, 1)
         return pattern_matching(lons, lats, self.n1, x1, y1, self.n2, x2, y2, **kwargs)
+
+    def get_warped_image(self, lons, lats, lon2, lat2, to=1, **kwargs):
+        """One image of the pair resampled into the other's frame along a drift grid (not the reference's; ``libwarp``).
+
+        lons, lats : (R, C) grid of start positions on image 1, as given to ``get_drift_PM``
+        lon2, lat2 : (R, C) the positions of the same ice on image 2, as ``get_drift_PM`` returns them (NaN: no result)
+        to : 1 - image 2 in the frame of image 1 (motion compensated: to look at, or to difference with image 1);
+             2 - image 1 in the frame of image 2
+        Other keyword arguments are those of ``libwarp.warp_image`` (``valid=``, ``order=``, ``fill=``, ``return_covered=``...).
+
+        Returns the warped uint8 image with the shape of the frame it is in (and the covered mask on request)."""
+        import numpy as np
+        shape = np.shape(lons)
+        if len(shape) != 2 or any(np.shape(a) != shape for a in (lats, lon2, lat2)):
+            raise ValueError('get_warped_image: lons, lats, lon2, lat2 must be 2-D grids of one shape (got %s)'
+                             % ([np.shape(a) for a in (lons, lats, lon2, lat2)],))
+        if to not in (1, 2):
+            raise ValueError('get_warped_image: to must be 1 or 2 (got %r)' % (to,))
+        x1, y1 = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n1.transform_points(lons, lats, 1)]
+        x2, y2 = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n2.transform_points(lon2, lat2, 1)]
+        if to == 1:
+            return warp_image(self.n2[1], x1, y1, x2, y2, out_shape=tuple(self.n1.shape()), **kwargs)
+        return warp_image(self.n1[1], x2, y2, x1, y1, out_shape=tuple(self.n2.shape()), **kwargs)
