@@ -625,6 +625,28 @@ def get_hessian(ccm, flags=HES_NORM, device=0):
     return out
 
 
+def _checker(unit, index_error=None):
+    """The return-code check of one unit of the library: raises SidPmError with the unit's own ``<unit>_last_error`` text
+    (IndexError for the code ``index_error``)."""
+    def check(rc):
+        if rc != 0:
+            msg = getattr(lib(), unit + '_last_error')().decode()
+            raise IndexError(msg) if rc == index_error else SidPmError(rc, msg)
+    return check
+
+
+_ft_check, _stage_check, _fg_check = _checker('sid_ft'), _checker('sid_stage'), _checker('sid_fg')
+_defor_check, _grid_check, _warp_check = _checker('sid_defor', DEFOR_ERR_INDEX), _checker('sid_grid'), _checker('sid_warp')
+_prep_check, _mask_check = _checker('sid_prep'), _checker('sid_mask')
+
+
+def _vp(p):
+    """An optional pointer argument: a raw address (0 or None: null) or a NumPy array (None: null)."""
+    if isinstance(p, np.ndarray):
+        p = p.ctypes.data
+    return C.c_void_p(int(p)) if p else None
+
+
 def ft_knn2(desc1, desc2, device=0):
     """Two nearest train descriptors (Hamming) of every query descriptor: include/sid_ft.h sid_ft_knn2.
 
@@ -634,16 +656,9 @@ def ft_knn2(desc1, desc2, device=0):
     idx = np.empty((len(d1), 2), dtype=np.int32)
     dist = np.empty((len(d1), 2), dtype=np.int32)
     L = lib()
-    rc = L.sid_ft_knn2(int(device), d1.ctypes.data_as(_u8p), len(d1), d2.ctypes.data_as(_u8p), len(d2),
-                       idx.ctypes.data_as(_i32p), dist.ctypes.data_as(_i32p))
-    if rc != 0:
-        raise SidPmError(rc, L.sid_ft_last_error().decode())
+    _ft_check(L.sid_ft_knn2(int(device), d1.ctypes.data_as(_u8p), len(d1), d2.ctypes.data_as(_u8p), len(d2),
+                            idx.ctypes.data_as(_i32p), dist.ctypes.data_as(_i32p)))
     return idx, dist
-
-
-def _stage_check(rc):
-    if rc != 0:
-        raise SidPmError(rc, lib().sid_stage_last_error().decode())
 
 
 class _StageRoute(C.Structure):
@@ -680,10 +695,10 @@ class StageWorkspace(object):
         n = C.c_int64(0)
         if fractions is not None and len(fractions) > 0:
             f = np.ascontiguousarray(fractions, dtype=np.float64)
-            _stage_check(lib().sid_stage_begin_hint(self._h, C.c_void_p(int(ptr)), rows, cols, stride,
-                                                    f.ctypes.data_as(C.POINTER(C.c_double)), len(f), C.byref(n), C.c_void_p(int(stream))))
+            _stage_check(lib().sid_stage_begin_hint(self._h, _vp(ptr), rows, cols, stride,
+                                                    f.ctypes.data_as(C.POINTER(C.c_double)), len(f), C.byref(n), _vp(stream)))
         else:
-            _stage_check(lib().sid_stage_begin(self._h, C.c_void_p(int(ptr)), rows, cols, stride, C.byref(n), C.c_void_p(int(stream))))
+            _stage_check(lib().sid_stage_begin(self._h, _vp(ptr), rows, cols, stride, C.byref(n), _vp(stream)))
         return int(n.value)
 
     def order_stats(self, ranks):
@@ -706,7 +721,7 @@ class StageWorkspace(object):
 def stage_count_valid(ptr, rows, cols, stride, stream=0):
     """Non-NaN pixels of a device float32 image (include/sid_stage.h)."""
     n = C.c_int64(0)
-    _stage_check(lib().sid_stage_count_valid(C.c_void_p(int(ptr)), rows, cols, stride, C.byref(n), C.c_void_p(int(stream))))
+    _stage_check(lib().sid_stage_count_valid(_vp(ptr), rows, cols, stride, C.byref(n), _vp(stream)))
     return int(n.value)
 
 
@@ -714,14 +729,14 @@ def stage_order_stats(ptr, rows, cols, stride, ranks, stream=0):
     """Exact order statistics (0-based ranks among the non-NaN pixels) of a device float32 image."""
     r = np.ascontiguousarray(ranks, dtype=np.int64)
     out = np.empty(len(r), dtype=np.float32)
-    _stage_check(lib().sid_stage_order_stats(C.c_void_p(int(ptr)), rows, cols, stride, r.ctypes.data_as(C.POINTER(C.c_int64)),
-                                             len(r), out.ctypes.data_as(_f32p), C.c_void_p(int(stream))))
+    _stage_check(lib().sid_stage_order_stats(_vp(ptr), rows, cols, stride, r.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             len(r), out.ctypes.data_as(_f32p), _vp(stream)))
     return out
 
 
 def stage_scale_u8(ptr, rows, cols, stride, vmin, denom, out_ptr, out_stride, stream=0):
-    _stage_check(lib().sid_stage_scale_u8(C.c_void_p(int(ptr)), rows, cols, stride, float(vmin), float(denom),
-                                          C.c_void_p(int(out_ptr)), out_stride, C.c_void_p(int(stream))))
+    _stage_check(lib().sid_stage_scale_u8(_vp(ptr), rows, cols, stride, float(vmin), float(denom),
+                                          _vp(out_ptr), out_stride, _vp(stream)))
 
 
 def fg_interp_linear(pts, simplices, values, q, device=0, details=False):
@@ -735,10 +750,8 @@ def fg_interp_linear(pts, simplices, values, q, device=0, details=False):
     sx = np.empty(len(q), dtype=np.int32)
     dbt = np.empty(len(q), dtype=np.int32)
     L = lib()
-    rc = L.sid_fg_interp_linear(int(device), _p(pts, _f64p), len(pts), simp.ctypes.data_as(_i32p), len(simp), _p(values, _f64p),
-                                _p(q, _f64p), len(q), _p(out, _f64p), sx.ctypes.data_as(_i32p), dbt.ctypes.data_as(_i32p))
-    if rc != 0:
-        raise SidPmError(rc, L.sid_fg_last_error().decode())
+    _fg_check(L.sid_fg_interp_linear(int(device), _p(pts, _f64p), len(pts), simp.ctypes.data_as(_i32p), len(simp), _p(values, _f64p),
+                                     _p(q, _f64p), len(q), _p(out, _f64p), sx.ctypes.data_as(_i32p), dbt.ctypes.data_as(_i32p)))
     return (out, sx, dbt.astype(bool)) if details else out
 
 
@@ -747,9 +760,7 @@ def fg_nearest_dist(seeds, q, device=0):
     seeds, q = _f64(seeds), _f64(q)
     out = np.empty(len(q), dtype=np.float64)
     L = lib()
-    rc = L.sid_fg_nearest_dist(int(device), _p(seeds, _f64p), len(seeds), _p(q, _f64p), len(q), _p(out, _f64p))
-    if rc != 0:
-        raise SidPmError(rc, L.sid_fg_last_error().decode())
+    _fg_check(L.sid_fg_nearest_dist(int(device), _p(seeds, _f64p), len(seeds), _p(q, _f64p), len(q), _p(out, _f64p)))
     return out
 
 
@@ -759,9 +770,7 @@ def fg_distance_image(seeds, rows, cols, device=0):
     seeds = _f64(seeds)
     out = np.empty((int(rows), int(cols)), dtype=np.float64)
     L = lib()
-    rc = L.sid_fg_distance_image(int(device), _p(seeds, _f64p), len(seeds), int(rows), int(cols), _p(out, _f64p))
-    if rc != 0:
-        raise SidPmError(rc, L.sid_fg_last_error().decode())
+    _fg_check(L.sid_fg_distance_image(int(device), _p(seeds, _f64p), len(seeds), int(rows), int(cols), _p(out, _f64p)))
     return out
 
 
@@ -779,20 +788,10 @@ def fg_knn(seeds, values, q, k=5, max_dist=None, device=0, details=False):
     cnt = np.empty(len(q), dtype=np.int32)
     idx = np.empty((len(q), min(max(k, 0), 16)), dtype=np.int32)
     L = lib()
-    rc = L.sid_fg_knn(int(device), _p(seeds, _f64p), len(seeds), _p(values, _f64p), _p(q, _f64p), len(q), k,
-                      float('inf') if max_dist is None else float(max_dist), _p(out, _f64p),
-                      _p(cnt, _i32p) if details else None, _p(idx, _i32p) if details else None)
-    if rc != 0:
-        raise SidPmError(rc, L.sid_fg_last_error().decode())
+    _fg_check(L.sid_fg_knn(int(device), _p(seeds, _f64p), len(seeds), _p(values, _f64p), _p(q, _f64p), len(q), k,
+                           float('inf') if max_dist is None else float(max_dist), _p(out, _f64p),
+                           _p(cnt, _i32p) if details else None, _p(idx, _i32p) if details else None))
     return (out, cnt, idx) if details else out
-
-
-def _defor_check(rc):
-    if rc != 0:
-        msg = lib().sid_defor_last_error().decode()
-        if rc == DEFOR_ERR_INDEX:
-            raise IndexError(msg)
-        raise SidPmError(rc, msg)
 
 
 def defor_triangulation(x, y, u, v, t, device=0):
@@ -801,7 +800,7 @@ def defor_triangulation(x, y, u, v, t, device=0):
     m = len(t)
     out = [np.empty(m, dtype=np.float64) for _ in range(5)]
     _defor_check(lib().sid_defor_triangulation(int(device), *[_p(a, _f64p) for a in (x, y, u, v)], len(x),
-                                               C.c_void_p(t.ctypes.data), int(t.dtype == np.int64), m,
+                                               _vp(t), int(t.dtype == np.int64), m,
                                                *[_p(a, _f64p) for a in out]))
     return tuple(out)
 
@@ -816,15 +815,15 @@ def defor_elems(x, y, u, v, a, device=0):
 
 def defor_triangulation_device(x, y, u, v, n, t, t_int64, m, outs, stream):
     """``sid_defor_triangulation_device`` on raw device pointers (torch ``data_ptr()``): outs = (e1, e2, e3, a, p)."""
-    _defor_check(lib().sid_defor_triangulation_device(*[C.c_void_p(int(q)) for q in (x, y, u, v)], int(n), C.c_void_p(int(t)),
-                                                      int(bool(t_int64)), int(m), *[C.c_void_p(int(q)) for q in outs],
-                                                      C.c_void_p(int(stream))))
+    _defor_check(lib().sid_defor_triangulation_device(*[_vp(q) for q in (x, y, u, v)], int(n), _vp(t),
+                                                      int(bool(t_int64)), int(m), *[_vp(q) for q in outs],
+                                                      _vp(stream)))
 
 
 def defor_elems_device(x, y, u, v, a, m, outs, stream):
     """``sid_defor_elems_device`` on raw device pointers: x, y, u, v [3, m], a [m]; outs = (e1, e2, e3)."""
-    _defor_check(lib().sid_defor_elems_device(*[C.c_void_p(int(q)) for q in (x, y, u, v, a)], int(m),
-                                              *[C.c_void_p(int(q)) for q in outs], C.c_void_p(int(stream))))
+    _defor_check(lib().sid_defor_elems_device(*[_vp(q) for q in (x, y, u, v, a)], int(m),
+                                              *[_vp(q) for q in outs], _vp(stream)))
 
 
 def defor_debug_hypot(x, y, device=0):
@@ -836,11 +835,6 @@ def defor_debug_hypot(x, y, device=0):
     out = np.empty_like(x)
     _defor_check(lib().sid_defor_debug_hypot(int(device), _p(x, _f64p), _p(y, _f64p), x.size, _p(out, _f64p)))
     return out
-
-
-def _grid_check(rc):
-    if rc != 0:
-        raise SidPmError(rc, lib().sid_grid_last_error().decode())
 
 
 def _opt_u8(valid):
@@ -870,24 +864,15 @@ def grid_deformation(x, y, u, v, valid, diagonal, device=0):
 
 def grid_filter_device(u, v, valid, rows, cols, eps, threshold, radius, min_neighbours, keep, res, stream):
     """``sid_grid_filter_device`` on raw device pointers (torch ``data_ptr()``; valid 0 for none)."""
-    _grid_check(lib().sid_grid_filter_device(*[C.c_void_p(int(q)) for q in (u, v, valid)], int(rows), int(cols), float(eps),
-                                             float(threshold), int(radius), int(min_neighbours), C.c_void_p(int(keep)),
-                                             C.c_void_p(int(res)), C.c_void_p(int(stream))))
+    _grid_check(lib().sid_grid_filter_device(*[_vp(q) for q in (u, v, valid)], int(rows), int(cols), float(eps),
+                                             float(threshold), int(radius), int(min_neighbours), _vp(keep),
+                                             _vp(res), _vp(stream)))
 
 
 def grid_deformation_device(x, y, u, v, valid, rows, cols, diagonal, outs, stream):
     """``sid_grid_deformation_device`` on raw device pointers: outs = (e1, e2, e3, a, p, t)."""
-    _grid_check(lib().sid_grid_deformation_device(*[C.c_void_p(int(q)) for q in (x, y, u, v, valid)], int(rows), int(cols),
-                                                  int(diagonal), *[C.c_void_p(int(q)) for q in outs], C.c_void_p(int(stream))))
-
-
-def _warp_check(rc):
-    if rc != 0:
-        raise SidPmError(rc, lib().sid_warp_last_error().decode())
-
-
-def _vp_of(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else None
+    _grid_check(lib().sid_grid_deformation_device(*[_vp(q) for q in (x, y, u, v, valid)], int(rows), int(cols),
+                                                  int(diagonal), *[_vp(q) for q in outs], _vp(stream)))
 
 
 def warp_image(x, y, xs, ys, valid, src, dtype, src_shape, out_shape, order, fill, diagonal, flags, want_out, want_covered,
@@ -903,25 +888,20 @@ def warp_image(x, y, xs, ys, valid, src, dtype, src_shape, out_shape, order, fil
     map_y = np.empty((ro, co), dtype=np.float32) if want_maps else None
     stride = src.strides[0] // src.itemsize if src is not None and src.shape[0] > 1 else int(src_shape[1])
     _warp_check(lib().sid_warp_image(int(device), *[_p(a, _f64p) for a in (x, y, xs, ys)], _opt_u8(valid), rows, cols,
-                                     _vp_of(src), WARP_DTYPES[dtype], int(src_shape[0]), int(src_shape[1]), stride, ro, co,
-                                     int(order), float(fill), int(diagonal), int(flags), _vp_of(out), co, _vp_of(covered),
-                                     _vp_of(map_x), _vp_of(map_y)))
+                                     _vp(src), WARP_DTYPES[dtype], int(src_shape[0]), int(src_shape[1]), stride, ro, co,
+                                     int(order), float(fill), int(diagonal), int(flags), _vp(out), co, _vp(covered),
+                                     _vp(map_x), _vp(map_y)))
     return out, covered, map_x, map_y
 
 
 def warp_image_device(x, y, xs, ys, valid, rows, cols, src, dtype, src_shape, src_stride, out_shape, order, fill, diagonal,
                       flags, out, out_stride, covered, map_x, map_y, stream):
     """``sid_warp_image_device`` on raw device pointers (torch ``data_ptr()``; 0 for none)."""
-    vp = [C.c_void_p(int(q)) if q else None for q in (x, y, xs, ys, valid, src, out, covered, map_x, map_y)]
+    vp = [_vp(q) for q in (x, y, xs, ys, valid, src, out, covered, map_x, map_y)]
     _warp_check(lib().sid_warp_image_device(*vp[:5], int(rows), int(cols), vp[5], WARP_DTYPES[dtype], int(src_shape[0]),
                                             int(src_shape[1]), int(src_stride), int(out_shape[0]), int(out_shape[1]),
                                             int(order), float(fill), int(diagonal), int(flags), vp[6], int(out_stride),
-                                            vp[7], vp[8], vp[9], C.c_void_p(int(stream))))
-
-
-def _prep_check(rc):
-    if rc != 0:
-        raise SidPmError(rc, lib().sid_prep_last_error().decode())
+                                            vp[7], vp[8], vp[9], _vp(stream)))
 
 
 def _prep_coeffs(coeffs):
@@ -937,9 +917,9 @@ def prep_subsample(img, rows, cols, stride, ia, mask, dB, hh_factor, step, sub_p
     """``sid_prep_subsample`` on raw device pointers: ``img`` a pointer, ``ia`` / ``mask`` (pointer, row stride) or None."""
     ia_ptr, ia_stride = ia if ia is not None else (0, 0)
     m_ptr, m_stride = mask if mask is not None else (0, 0)
-    _prep_check(lib().sid_prep_subsample(C.c_void_p(int(img)), rows, cols, stride, C.c_void_p(int(ia_ptr) or None), ia_stride,
-                                         C.c_void_p(int(m_ptr) or None), m_stride, int(bool(dB)), float(hh_factor), int(step),
-                                         C.c_void_p(int(sub_ptr)), C.c_void_p(int(stream))))
+    _prep_check(lib().sid_prep_subsample(_vp(img), rows, cols, stride, _vp(ia_ptr), ia_stride,
+                                         _vp(m_ptr), m_stride, int(bool(dB)), float(hh_factor), int(step),
+                                         _vp(sub_ptr), _vp(stream)))
 
 
 def prep_apply(img, rows, cols, stride, ia, mask, dB, hh_factor, coeffs, out_ptr, out_stride, stream=0):
@@ -947,9 +927,9 @@ def prep_apply(img, rows, cols, stride, ia, mask, dB, hh_factor, coeffs, out_ptr
     ia_ptr, ia_stride = ia if ia is not None else (0, 0)
     m_ptr, m_stride = mask if mask is not None else (0, 0)
     keep, cp = _prep_coeffs(coeffs)
-    _prep_check(lib().sid_prep_apply(C.c_void_p(int(img)), rows, cols, stride, C.c_void_p(int(ia_ptr) or None), ia_stride,
-                                     C.c_void_p(int(m_ptr) or None), m_stride, int(bool(dB)), float(hh_factor), cp,
-                                     C.c_void_p(int(out_ptr)), out_stride, C.c_void_p(int(stream))))
+    _prep_check(lib().sid_prep_apply(_vp(img), rows, cols, stride, _vp(ia_ptr), ia_stride,
+                                     _vp(m_ptr), m_stride, int(bool(dB)), float(hh_factor), cp,
+                                     _vp(out_ptr), out_stride, _vp(stream)))
 
 
 def prep_spatial_mean(rows, cols, coeffs, out_ptr, out_stride, stream=0):
@@ -957,7 +937,7 @@ def prep_spatial_mean(rows, cols, coeffs, out_ptr, out_stride, stream=0):
     keep, cp = _prep_coeffs(coeffs)
     if cp is None:
         raise ValueError('six float64 coefficients expected')
-    _prep_check(lib().sid_prep_spatial_mean(rows, cols, cp, C.c_void_p(int(out_ptr)), out_stride, C.c_void_p(int(stream))))
+    _prep_check(lib().sid_prep_spatial_mean(rows, cols, cp, _vp(out_ptr), out_stride, _vp(stream)))
 
 
 def prep_debug_log10(first_bits, n):
@@ -968,18 +948,9 @@ def prep_debug_log10(first_bits, n):
     return int(counts[0]), int(counts[1])
 
 
-def _mask_check(rc):
-    if rc != 0:
-        raise SidPmError(rc, lib().sid_mask_last_error().decode())
-
-
 def mask_workspace_bytes(h, w):
     """``sid_mask_workspace_bytes``: device scratch for a water mask of ``h`` x ``w``."""
     return int(lib().sid_mask_workspace_bytes(int(h), int(w)))
-
-
-def _vp(ptr):
-    return C.c_void_p(int(ptr) or None)
 
 
 def mask_landmask(wm, h, w, H, W, work_ptr, mask, wmz, stream=0):
@@ -987,7 +958,7 @@ def mask_landmask(wm, h, w, H, W, work_ptr, mask, wmz, stream=0):
     m_ptr, m_stride = mask if mask is not None else (0, 0)
     z_ptr, z_stride = wmz if wmz is not None else (0, 0)
     _mask_check(lib().sid_mask_landmask(_vp(wm[0]), int(h), int(w), int(wm[1]), int(H), int(W), _vp(work_ptr), _vp(m_ptr), m_stride,
-                                        _vp(z_ptr), z_stride, C.c_void_p(int(stream))))
+                                        _vp(z_ptr), z_stride, _vp(stream)))
 
 
 def mask_invalid(wm, h, w, H, W, work_ptr, img, dB, ia, hh_factor, mask, wmz=None, stream=0):
@@ -998,4 +969,4 @@ def mask_invalid(wm, h, w, H, W, work_ptr, img, dB, ia, hh_factor, mask, wmz=Non
     z_ptr, z_stride = wmz if wmz is not None else (0, 0)
     _mask_check(lib().sid_mask_invalid(_vp(w_ptr), int(h), int(w), int(w_stride), int(H), int(W), _vp(work_ptr), _vp(img[0]), int(img[1]),
                                        int(bool(dB)), _vp(ia_ptr), int(ia_stride), float(hh_factor), _vp(mask[0]), int(mask[1]),
-                                       _vp(z_ptr), int(z_stride), C.c_void_p(int(stream))))
+                                       _vp(z_ptr), int(z_stride), _vp(stream)))

@@ -5,25 +5,13 @@
 // serves the host check of sid_defor_debug_hypot(-1, ...).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <mutex>
 
 #include "../../include/sid_defor.h"
-#include "../../include/sid_pm.h"
 #include "defor_elem.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 constexpr int kBlock = 256;
 constexpr int64_t kMaxElems = (int64_t)0x7fffffff * kBlock;     // grid.x limit
@@ -88,26 +76,23 @@ __global__ __launch_bounds__(kBlock) void k_defor_hypot(const double *__restrict
     if (k < n) out[k] = sid_defor::hypot64(x[k], y[k]);
 }
 
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
-// Per device: a grow-only scratch block for the host-buffer entry points (no hipMalloc / hipFree per call), the index flag
-// and its pinned host copy.  The flag is never cleared: each call has its own number and an error is "flag == number".
-// Calls are serialised by the mutex.
-struct Dev { unsigned char *blk = nullptr; size_t cap = 0; uint32_t *d_flag = nullptr; uint32_t *h_flag = nullptr; uint32_t gen = 0; };
-std::mutex g_mu;
-Dev g_dev[16];
+// Per device, beside the pool's staging block: the index flag and its pinned host copy.  The flag is never cleared: each call
+// has its own number and an error is "flag == number".  Calls are serialised by the pool's mutex.
+struct Flag {
+    uint32_t *d_flag = nullptr, *h_flag = nullptr, gen = 0;
+    bool cached() const { return d_flag != nullptr; }
+    void free()
+    {
+        if (d_flag) (void)hipFree(d_flag);
+        if (h_flag) (void)hipHostFree(h_flag);
+    }
+};
+using Dev = DevicePool<Flag>::Slot;
+DevicePool<Flag> g_pool;
 
 int current_device(int &dev)
 {
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(SID_PM_ERR_NODEVICE, "no current HIP device");
-    return SID_PM_OK;
-}
-
-int pick_device(int device, int &prev)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n || device >= 16) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
-    (void)hipGetDevice(&prev); (void)hipSetDevice(device);
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return fail(SID_PM_ERR_NODEVICE, "no current HIP device");
     return SID_PM_OK;
 }
 
@@ -125,27 +110,12 @@ int flag_ready(Dev &d)
     return SID_PM_OK;
 }
 
-int reserve(Dev &d, size_t bytes)
-{
-    if (d.cap >= bytes) return SID_PM_OK;
-    if (d.blk) (void)hipFree(d.blk);
-    d.blk = nullptr; d.cap = 0;
-    const size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d.blk), want);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SID_PM_ERR_NOMEM : SID_PM_ERR_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
-    d.cap = want;
-    return SID_PM_OK;
-}
-
-size_t up(size_t b) { return (b + 255) / 256 * 256; }
-
 unsigned blocks(int64_t m) { return (unsigned)((m + kBlock - 1) / kBlock); }
 
 // Launch the triangle kernel and queue the flag's copy; the caller waits for the stream and calls flag_check.
 int launch_tri(Dev &d, const double *x, const double *y, const double *u, const double *v, int64_t n, const void *t, int t_int64,
                int64_t m, double *e1, double *e2, double *e3, double *a, double *p, hipStream_t st)
 {
-    int rc = SID_PM_OK;
     const uint32_t gen = ++d.gen ? d.gen : ++d.gen;                // (0 is the flag's initial value: never a call's number)
     if (t_int64)
         hipLaunchKernelGGL(k_defor_tri<int64_t>, dim3(blocks(m)), dim3(kBlock), 0, st, x, y, u, v, n, (const int64_t *)t, m,
@@ -155,13 +125,20 @@ int launch_tri(Dev &d, const double *x, const double *y, const double *u, const 
                            e1, e2, e3, a, p, d.d_flag, gen);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(d.h_flag, d.d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-done:
-    return rc;
+    return SID_PM_OK;
 }
 
 int flag_check(const Dev &d)
 {
     if (*d.h_flag == d.gen) return fail(SID_DEFOR_ERR_INDEX, "an index of t lies outside [-n, n)");
+    return SID_PM_OK;
+}
+
+int launch_elems(const double *x, const double *y, const double *u, const double *v, const double *a, int64_t m,
+                 double *e1, double *e2, double *e3, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_defor_elems, dim3(blocks(m)), dim3(kBlock), 0, st, x, y, u, v, a, m, e1, e2, e3);
+    HIP_TRY(hipGetLastError());
     return SID_PM_OK;
 }
 
@@ -186,129 +163,87 @@ int check_elem_args(const void *x, const void *y, const void *u, const void *v, 
 
 SID_EXPORT const char *sid_defor_last_error(void) { return g_err; }
 
-SID_EXPORT int sid_defor_release(int device)
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    for (int i = 0; i < 16; ++i) {
-        if (device >= 0 && i != device) continue;
-        Dev &d = g_dev[i];
-        if (!d.blk && !d.d_flag) continue;
-        (void)hipSetDevice(i);
-        if (d.blk) (void)hipFree(d.blk);
-        if (d.d_flag) (void)hipFree(d.d_flag);
-        if (d.h_flag) (void)hipHostFree(d.h_flag);
-        d = Dev();
-    }
-    (void)hipSetDevice(prev);
-    return SID_PM_OK;
-}
+SID_EXPORT int sid_defor_release(int device) { return g_pool.release(device); }
 
 SID_EXPORT int sid_defor_triangulation_device(const double *x, const double *y, const double *u, const double *v, int64_t n,
                                               const void *t, int t_int64, int64_t m,
                                               double *e1, double *e2, double *e3, double *a, double *p, void *hip_stream)
 {
-    if (int rc0 = check_tri_args(x, y, u, v, n, t, m, e1, e2, e3, a, p)) return rc0;
+    if (int rc = check_tri_args(x, y, u, v, n, t, m, e1, e2, e3, a, p)) return rc;
     if (m == 0) return SID_PM_OK;
     int dev = 0;
-    if (int rc0 = current_device(dev)) return rc0;
+    if (int rc = current_device(dev)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    int rc = SID_PM_OK;
-    std::lock_guard<std::mutex> lock(g_mu);
-    Dev &d = g_dev[dev];
-    if ((rc = flag_ready(d))) return rc;
-    if ((rc = launch_tri(d, x, y, u, v, n, t, t_int64, m, e1, e2, e3, a, p, st))) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mutex(dev));
+    Dev &d = g_pool.slot[dev];
+    if (int rc = flag_ready(d)) return rc;
+    if (int rc = launch_tri(d, x, y, u, v, n, t, t_int64, m, e1, e2, e3, a, p, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    rc = flag_check(d);
-done:
-    return rc;
+    return flag_check(d);
 }
 
 SID_EXPORT int sid_defor_elems_device(const double *x, const double *y, const double *u, const double *v, const double *a, int64_t m,
                                       double *e1, double *e2, double *e3, void *hip_stream)
 {
-    if (int rc0 = check_elem_args(x, y, u, v, a, m, e1, e2, e3)) return rc0;
+    if (int rc = check_elem_args(x, y, u, v, a, m, e1, e2, e3)) return rc;
     if (m == 0) return SID_PM_OK;
-    int rc = SID_PM_OK;
-    hipLaunchKernelGGL(k_defor_elems, dim3(blocks(m)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(hip_stream),
-                       x, y, u, v, a, m, e1, e2, e3);
-    HIP_TRY(hipGetLastError());
-done:
-    return rc;
+    return launch_elems(x, y, u, v, a, m, e1, e2, e3, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 SID_EXPORT int sid_defor_triangulation(int device, const double *x, const double *y, const double *u, const double *v, int64_t n,
                                        const void *t, int t_int64, int64_t m,
                                        double *e1, double *e2, double *e3, double *a, double *p)
 {
-    if (int rc0 = check_tri_args(x, y, u, v, n, t, m, e1, e2, e3, a, p)) return rc0;
+    if (int rc = check_tri_args(x, y, u, v, n, t, m, e1, e2, e3, a, p)) return rc;
     if (m == 0) return SID_PM_OK;
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        Dev &d = g_dev[device];
-        const size_t nb = sizeof(double) * (size_t)n, mb = sizeof(double) * (size_t)m, tb = (t_int64 ? 8 : 4) * 3 * (size_t)m;
-        double *dx, *dy, *du, *dv, *out;
-        unsigned char *dt;
-        if ((rc = flag_ready(d)) || (rc = reserve(d, 4 * up(nb) + up(tb) + 5 * up(mb)))) goto done;
-        dx = reinterpret_cast<double *>(d.blk); dy = dx + up(nb) / 8; du = dy + up(nb) / 8; dv = du + up(nb) / 8;
-        dt = reinterpret_cast<unsigned char *>(dv + up(nb) / 8);
-        out = reinterpret_cast<double *>(dt + up(tb));
-        HIP_TRY(hipMemcpyAsync(dx, x, nb, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(dy, y, nb, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(dv, v, nb, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(dt, t, tb, hipMemcpyHostToDevice, 0));
-        {
-            const size_t o = up(mb) / 8;
-            if ((rc = launch_tri(d, dx, dy, du, dv, n, dt, t_int64, m, out, out + o, out + 2 * o, out + 3 * o, out + 4 * o, 0))) goto done;
-            double *dst[5] = {e1, e2, e3, a, p};
-            for (int j = 0; j < 5; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out + j * o, mb, hipMemcpyDeviceToHost, 0));
-        }
-        HIP_TRY(hipStreamSynchronize(0));
-        rc = flag_check(d);
-    }
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    Dev &d = g_pool.slot[device];
+    const size_t nb = sizeof(double) * (size_t)n, mb = sizeof(double) * (size_t)m, tb = (t_int64 ? 8 : 4) * 3 * (size_t)m;
+    double *in[4], *out[5];
+    unsigned char *dt;
+    if (int rc = flag_ready(d)) return rc;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            for (double *&q : in) q = c.take<double>((size_t)n);
+            dt = c.take<unsigned char>(tb);
+            for (double *&q : out) q = c.take<double>((size_t)m);
+        }))
+        return rc;
+    const double *src[4] = {x, y, u, v};
+    for (int j = 0; j < 4; ++j) HIP_TRY(hipMemcpyAsync(in[j], src[j], nb, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(dt, t, tb, hipMemcpyHostToDevice, 0));
+    if (int rc = launch_tri(d, in[0], in[1], in[2], in[3], n, dt, t_int64, m, out[0], out[1], out[2], out[3], out[4], 0)) return rc;
+    double *dst[5] = {e1, e2, e3, a, p};
+    for (int j = 0; j < 5; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out[j], mb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return flag_check(d);
 }
 
 SID_EXPORT int sid_defor_elems(int device, const double *x, const double *y, const double *u, const double *v, const double *a, int64_t m,
                                double *e1, double *e2, double *e3)
 {
-    if (int rc0 = check_elem_args(x, y, u, v, a, m, e1, e2, e3)) return rc0;
+    if (int rc = check_elem_args(x, y, u, v, a, m, e1, e2, e3)) return rc;
     if (m == 0) return SID_PM_OK;
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        Dev &d = g_dev[device];
-        const size_t mb = sizeof(double) * (size_t)m, o = up(mb) / 8, o3 = up(3 * mb) / 8;
-        double *in, *out;
-        if ((rc = reserve(d, 4 * up(3 * mb) + 4 * up(mb)))) goto done;
-        in = reinterpret_cast<double *>(d.blk);                          // x, y, u, v [3][m] each, then a, then e1, e2, e3
-        out = in + 4 * o3 + o;
-        {
-            const double *src[4] = {x, y, u, v};
-            for (int j = 0; j < 4; ++j) HIP_TRY(hipMemcpyAsync(in + j * o3, src[j], 3 * mb, hipMemcpyHostToDevice, 0));
-            HIP_TRY(hipMemcpyAsync(in + 4 * o3, a, mb, hipMemcpyHostToDevice, 0));
-        }
-        hipLaunchKernelGGL(k_defor_elems, dim3(blocks(m)), dim3(kBlock), 0, 0, in, in + o3, in + 2 * o3, in + 3 * o3, in + 4 * o3, m,
-                           out, out + o, out + 2 * o);
-        HIP_TRY(hipGetLastError());
-        {
-            double *dst[3] = {e1, e2, e3};
-            for (int j = 0; j < 3; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out + j * o, mb, hipMemcpyDeviceToHost, 0));
-        }
-        HIP_TRY(hipStreamSynchronize(0));
-    }
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    const size_t mb = sizeof(double) * (size_t)m;
+    double *in[4], *da, *out[3];                                         // x, y, u, v [3][m] each, then a, then e1, e2, e3
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            for (double *&q : in) q = c.take<double>(3 * (size_t)m);
+            da = c.take<double>((size_t)m);
+            for (double *&q : out) q = c.take<double>((size_t)m);
+        }))
+        return rc;
+    const double *src[4] = {x, y, u, v};
+    for (int j = 0; j < 4; ++j) HIP_TRY(hipMemcpyAsync(in[j], src[j], 3 * mb, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(da, a, mb, hipMemcpyHostToDevice, 0));
+    if (int rc = launch_elems(in[0], in[1], in[2], in[3], da, m, out[0], out[1], out[2], 0)) return rc;
+    double *dst[3] = {e1, e2, e3};
+    for (int j = 0; j < 3; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out[j], mb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
 }
 
 SID_EXPORT int sid_defor_debug_hypot(int device, const double *x, const double *y, int64_t n, double *out)
@@ -319,23 +254,17 @@ SID_EXPORT int sid_defor_debug_hypot(int device, const double *x, const double *
         for (int64_t i = 0; i < n; ++i) out[i] = sid_defor::hypot64(x[i], y[i]);
         return SID_PM_OK;
     }
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        Dev &d = g_dev[device];
-        const size_t nb = sizeof(double) * (size_t)n, o = up(nb) / 8;
-        double *dx;
-        if ((rc = reserve(d, 3 * up(nb)))) goto done;
-        dx = reinterpret_cast<double *>(d.blk);
-        HIP_TRY(hipMemcpyAsync(dx, x, nb, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(dx + o, y, nb, hipMemcpyHostToDevice, 0));
-        hipLaunchKernelGGL(k_defor_hypot, dim3(blocks(n)), dim3(kBlock), 0, 0, dx, dx + o, n, dx + 2 * o);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(out, dx + 2 * o, nb, hipMemcpyDeviceToHost));
-    }
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    const size_t nb = sizeof(double) * (size_t)n;
+    double *dx, *dy, *dout;
+    if (int rc = g_pool.carve(device, [&](Carver &c) { dx = c.take<double>((size_t)n); dy = c.take<double>((size_t)n); dout = c.take<double>((size_t)n); }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(dx, x, nb, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(dy, y, nb, hipMemcpyHostToDevice, 0));
+    hipLaunchKernelGGL(k_defor_hypot, dim3(blocks(n)), dim3(kBlock), 0, 0, dx, dy, n, dout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout, nb, hipMemcpyDeviceToHost));
+    s.done();
+    return SID_PM_OK;
 }

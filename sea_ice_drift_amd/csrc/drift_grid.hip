@@ -8,25 +8,13 @@
 //                  structure-of-arrays.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <mutex>
 
 #include "../../include/sid_grid.h"
-#include "../../include/sid_pm.h"
 #include "grid_cell.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 constexpr int kTR = SID_GRID_TILE_ROWS, kTC = SID_GRID_TILE_COLS, kBlock = kTR * kTC;
 static_assert(kBlock == 256, "the filter's tile is one 256-thread workgroup");
@@ -176,83 +164,34 @@ int check_defor_args(const void *x, const void *y, const void *u, const void *v,
 }
 
 // ---------------------------------------------------------------- launches
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
 int launch_filter(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols, double eps, double threshold,
                   int radius, int min_neighbours, uint8_t *keep, double *res, hipStream_t st)
 {
-    int rc = SID_PM_OK;
     const int64_t tiles_r = (rows + kTR - 1) / kTR, tiles_c = (cols + kTC - 1) / kTC;     // rows * cols < 2^31: so is the product
     hipLaunchKernelGGL(k_grid_filter, dim3((unsigned)(tiles_r * tiles_c)), dim3(kBlock), filter_lds_bytes(radius), st,
                        u, v, valid, rows, cols, tiles_c, eps, threshold, radius, min_neighbours, keep, res);
     HIP_TRY(hipGetLastError());
-done:
-    return rc;
+    return SID_PM_OK;
 }
 
 int launch_defor(const double *x, const double *y, const double *u, const double *v, const uint8_t *valid, int64_t rows,
                  int64_t cols, int diagonal, double *e1, double *e2, double *e3, double *a, double *p, int32_t *t, hipStream_t st)
 {
-    int rc = SID_PM_OK;
     const int64_t cells = (rows - 1) * (cols - 1);
     hipLaunchKernelGGL(k_grid_defor, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        x, y, u, v, valid, cols, diagonal, cells, e1, e2, e3, a, p, t);
     HIP_TRY(hipGetLastError());
-done:
-    return rc;
-}
-
-// Per device: a grow-only scratch block for the host-buffer entry points (no hipMalloc / hipFree per call once warm).  Calls
-// are serialised by the mutex.
-struct Dev { unsigned char *blk = nullptr; size_t cap = 0; };
-std::mutex g_mu;
-Dev g_dev[16];
-
-int pick_device(int device, int &prev)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n || device >= 16) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
-    (void)hipGetDevice(&prev); (void)hipSetDevice(device);
     return SID_PM_OK;
 }
 
-int reserve(Dev &d, size_t bytes)
-{
-    if (d.cap >= bytes) return SID_PM_OK;
-    if (d.blk) (void)hipFree(d.blk);
-    d.blk = nullptr; d.cap = 0;
-    const size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d.blk), want);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SID_PM_ERR_NOMEM : SID_PM_ERR_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
-    d.cap = want;
-    return SID_PM_OK;
-}
-
-size_t up(size_t b) { return (b + 255) / 256 * 256; }
+// The staging block of the two host-buffer entry points, which carve it differently; calls are serialised by its mutex
+DevicePool<> g_pool;
 
 }  // namespace
 
 SID_EXPORT const char *sid_grid_last_error(void) { return g_err; }
 
-SID_EXPORT int sid_grid_release(int device)
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    int prev = 0;
-    bool any = false;
-    for (int i = 0; i < 16; ++i) any = any || ((device < 0 || i == device) && g_dev[i].blk);
-    if (!any) return SID_PM_OK;
-    (void)hipGetDevice(&prev);
-    for (int i = 0; i < 16; ++i) {
-        if (device >= 0 && i != device) continue;
-        Dev &d = g_dev[i];
-        if (!d.blk) continue;
-        (void)hipSetDevice(i);
-        (void)hipFree(d.blk);
-        d = Dev();
-    }
-    (void)hipSetDevice(prev);
-    return SID_PM_OK;
-}
+SID_EXPORT int sid_grid_release(int device) { return g_pool.release(device); }
 
 SID_EXPORT int sid_grid_filter_device(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,
                                       double eps, double threshold, int radius, int min_neighbours, uint8_t *keep, double *res,
@@ -276,82 +215,65 @@ SID_EXPORT int sid_grid_deformation_device(const double *x, const double *y, con
 SID_EXPORT int sid_grid_filter(int device, const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,
                                double eps, double threshold, int radius, int min_neighbours, uint8_t *keep, double *res)
 {
-    if (int rc0 = check_filter_args(u, v, rows, cols, eps, threshold, radius, min_neighbours, keep, res)) return rc0;
+    if (int rc = check_filter_args(u, v, rows, cols, eps, threshold, radius, min_neighbours, keep, res)) return rc;
     if (rows * cols == 0) return SID_PM_OK;
     if (device == -1) {
         host_filter(u, v, valid, rows, cols, eps, threshold, radius, min_neighbours, keep, res);
         return SID_PM_OK;
     }
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        Dev &d = g_dev[device];
-        const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n, o = up(nb) / 8;
-        double *du, *dres;
-        uint8_t *dvalid, *dkeep;
-        if ((rc = reserve(d, 3 * up(nb) + 2 * up(n)))) goto done;
-        du = reinterpret_cast<double *>(d.blk);                          // u, v, res, then valid, keep
-        dres = du + 2 * o;
-        dvalid = reinterpret_cast<uint8_t *>(du + 3 * o);
-        dkeep = dvalid + up(n);
-        HIP_TRY(hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(du + o, v, nb, hipMemcpyHostToDevice, 0));
-        if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
-        if ((rc = launch_filter(du, du + o, valid ? dvalid : nullptr, rows, cols, eps, threshold, radius, min_neighbours, dkeep, dres, 0)))
-            goto done;
-        HIP_TRY(hipMemcpyAsync(keep, dkeep, n, hipMemcpyDeviceToHost, 0));
-        HIP_TRY(hipMemcpyAsync(res, dres, nb, hipMemcpyDeviceToHost, 0));
-        HIP_TRY(hipStreamSynchronize(0));
-    }
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n;
+    double *du, *dv, *dres;
+    uint8_t *dvalid, *dkeep;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            du = c.take<double>(n); dv = c.take<double>(n); dres = c.take<double>(n);
+            dvalid = c.take<uint8_t>(n, valid != nullptr); dkeep = c.take<uint8_t>(n);
+        }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(dv, v, nb, hipMemcpyHostToDevice, 0));
+    if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
+    if (int rc = launch_filter(du, dv, dvalid, rows, cols, eps, threshold, radius, min_neighbours, dkeep, dres, 0)) return rc;
+    HIP_TRY(hipMemcpyAsync(keep, dkeep, n, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpyAsync(res, dres, nb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
 }
 
 SID_EXPORT int sid_grid_deformation(int device, const double *x, const double *y, const double *u, const double *v,
                                     const uint8_t *valid, int64_t rows, int64_t cols, int diagonal,
                                     double *e1, double *e2, double *e3, double *a, double *p, int32_t *t)
 {
-    if (int rc0 = check_defor_args(x, y, u, v, rows, cols, diagonal, e1, e2, e3, a, p, t)) return rc0;
+    if (int rc = check_defor_args(x, y, u, v, rows, cols, diagonal, e1, e2, e3, a, p, t)) return rc;
     if (rows < 2 || cols < 2) return SID_PM_OK;
     if (device == -1) {
         for (int64_t k = 0; k < (rows - 1) * (cols - 1); ++k) one_cell(x, y, u, v, valid, cols, diagonal, k, e1, e2, e3, a, p, t);
         return SID_PM_OK;
     }
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        Dev &d = g_dev[device];
-        const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n, o = up(nb) / 8;
-        const size_t m2 = 2 * (size_t)((rows - 1) * (cols - 1)), mb = sizeof(double) * m2, om = up(mb) / 8, tb = sizeof(int32_t) * 3 * m2;
-        double *in, *out;
-        int32_t *dt;
-        uint8_t *dvalid;
-        if ((rc = reserve(d, 4 * up(nb) + 5 * up(mb) + up(tb) + up(n)))) goto done;
-        in = reinterpret_cast<double *>(d.blk);                          // x, y, u, v, then e1, e2, e3, a, p, then t, then valid
-        out = in + 4 * o;
-        dt = reinterpret_cast<int32_t *>(out + 5 * om);
-        dvalid = reinterpret_cast<uint8_t *>(dt) + up(tb);
-        {
-            const double *src[4] = {x, y, u, v};
-            for (int j = 0; j < 4; ++j) HIP_TRY(hipMemcpyAsync(in + j * o, src[j], nb, hipMemcpyHostToDevice, 0));
-        }
-        if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
-        if ((rc = launch_defor(in, in + o, in + 2 * o, in + 3 * o, valid ? dvalid : nullptr, rows, cols, diagonal,
-                               out, out + om, out + 2 * om, out + 3 * om, out + 4 * om, dt, 0)))
-            goto done;
-        {
-            double *dst[5] = {e1, e2, e3, a, p};
-            for (int j = 0; j < 5; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out + j * om, mb, hipMemcpyDeviceToHost, 0));
-        }
-        HIP_TRY(hipMemcpyAsync(t, dt, tb, hipMemcpyDeviceToHost, 0));
-        HIP_TRY(hipStreamSynchronize(0));
-    }
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n;
+    const size_t m2 = 2 * (size_t)((rows - 1) * (cols - 1)), mb = sizeof(double) * m2, tb = sizeof(int32_t) * 3 * m2;
+    double *in[4], *out[5];
+    int32_t *dt;
+    uint8_t *dvalid;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            for (double *&q : in) q = c.take<double>(n);
+            for (double *&q : out) q = c.take<double>(m2);
+            dt = c.take<int32_t>(3 * m2);
+            dvalid = c.take<uint8_t>(n, valid != nullptr);
+        }))
+        return rc;
+    const double *src[4] = {x, y, u, v};
+    for (int j = 0; j < 4; ++j) HIP_TRY(hipMemcpyAsync(in[j], src[j], nb, hipMemcpyHostToDevice, 0));
+    if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
+    if (int rc = launch_defor(in[0], in[1], in[2], in[3], dvalid, rows, cols, diagonal, out[0], out[1], out[2], out[3], out[4], dt, 0)) return rc;
+    double *dst[5] = {e1, e2, e3, a, p};
+    for (int j = 0; j < 5; ++j) HIP_TRY(hipMemcpyAsync(dst[j], out[j], mb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpyAsync(t, dt, tb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
 }

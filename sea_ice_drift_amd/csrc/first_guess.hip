@@ -9,26 +9,15 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <float.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <mutex>
+#include <stdlib.h>
 #include <vector>
 
 #include "../../include/sid_fg.h"
-#include "../../include/sid_pm.h"
 #include "fg_knn.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 struct Simp { double t00, t01, t10, t11, rx, ry; int v0, v1, v2, ok; };
 
@@ -443,58 +432,18 @@ void knn_launch(const KnnArgs &a)
     else hipLaunchKernelGGL(k_knn<K>, blocks, dim3(256), 0, 0, a.seeds, a.values, a.ns, a.q, a.nq, a.k, a.m2, a.out, a.count, a.index);
 }
 
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
+// Device scratch of the entry points: one grow-only block per device, carved per call (no hipMalloc / hipFree per call - seven
+// and three of them cost about as much as the kernels).  Calls are serialised by the pool's mutex.
+DevicePool<> g_pool;
 
-// Device scratch of the two entry points: one grow-only block per device, carved per call (no hipMalloc / hipFree per
-// call - seven and three of them cost about as much as the kernels).  Calls are serialised by the pool's mutex.
-struct Pool { unsigned char *p = nullptr; size_t cap = 0; };
-std::mutex g_pool_mu;
-Pool g_pool[16];
-
-struct Carver {
-    unsigned char *base; size_t off = 0;
-    explicit Carver(unsigned char *b) : base(b) {}
-    template <typename T> T *take(size_t n) { T *r = reinterpret_cast<T *>(base + off); off += (n * sizeof(T) + 255) / 256 * 256; return r; }
+struct Box {
+    double x_lo = INFINITY, x_hi = -INFINITY, y_lo = INFINITY, y_hi = -INFINITY;
+    void add(double x, double y) { x_lo = fmin(x_lo, x); x_hi = fmax(x_hi, x); y_lo = fmin(y_lo, y); y_hi = fmax(y_hi, y); }
 };
-
-int pool_reserve(int device, size_t bytes, unsigned char **out)
-{
-    if (device < 0 || device >= 16) return fail(SID_PM_ERR_ARG, "device index out of range");
-    Pool &pl = g_pool[device];
-    if (pl.cap < bytes) {
-        if (pl.p) (void)hipFree(pl.p);
-        pl.p = nullptr; pl.cap = 0;
-        const size_t want = bytes + bytes / 4;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&pl.p), want);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SID_PM_ERR_NOMEM : SID_PM_ERR_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
-        pl.cap = want;
-    }
-    *out = pl.p;
-    return SID_PM_OK;
-}
-
-int pick_device(int device, int &prev)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
-    (void)hipGetDevice(&prev); (void)hipSetDevice(device);
-    return SID_PM_OK;
-}
 
 }  // namespace
 
-SID_EXPORT int sid_fg_release(int device)
-{
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    for (int d = 0; d < 16; ++d) {
-        if (device >= 0 && d != device) continue;
-        if (g_pool[d].p) { (void)hipSetDevice(d); (void)hipFree(g_pool[d].p); g_pool[d].p = nullptr; g_pool[d].cap = 0; }
-    }
-    (void)hipSetDevice(prev);
-    return SID_PM_OK;
-}
+SID_EXPORT int sid_fg_release(int device) { return g_pool.release(device); }
 
 SID_EXPORT const char *sid_fg_last_error(void) { return g_err; }
 
@@ -503,86 +452,133 @@ SID_EXPORT int sid_fg_interp_linear(int device, const double *pts, int64_t n_pts
 {
     if (n_q == 0) return SID_PM_OK;
     if (!pts || !simplices || !values || !q || !out || n_pts < 3 || n_simp < 1 || n_q < 0 || n_simp >= 0x7f7f7f7f) return fail(SID_PM_ERR_ARG, "bad argument");
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
     // bucket lists of the uniform grid: room for 8 entries per simplex on average (a Delaunay triangle of scattered points
     // touches 2-4 cells); a triangulation that needs more - long slivers across the whole box - takes the brute-force pass
     const int64_t grid_cap = 8 * n_simp + kGrid * kGrid;
-    const bool want_grid = getenv("SID_FG_NO_GRID") == nullptr;
-    const size_t need = up(sizeof(double) * 2 * n_pts) * 2 + up(sizeof(double) * 2 * n_q) * 2 + up(sizeof(int32_t) * 3 * n_simp) +
-                        up(sizeof(Simp) * n_simp) + up(sizeof(int32_t) * n_q) * 5 + 256 +
-                        up(sizeof(int32_t) * (kGrid * kGrid + 1)) * 2 + up(sizeof(int32_t) * grid_cap);
-    unsigned char *blk = nullptr;
-    double *d_pts = nullptr, *d_val = nullptr, *d_q = nullptr, *d_out = nullptr; int32_t *d_simp = nullptr, *d_loc = nullptr, *d_near = nullptr, *d_sx = nullptr, *d_dbt = nullptr, *d_list = nullptr, *d_nlist = nullptr; Simp *d_t = nullptr;
-    int32_t *d_cnt = nullptr, *d_start = nullptr, *d_ids = nullptr;
+    double *d_pts, *d_val, *d_q, *d_out;
+    int32_t *d_simp, *d_loc, *d_near, *d_sx, *d_dbt, *d_list, *d_nlist, *d_cnt, *d_start, *d_ids;
+    Simp *d_t;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            d_pts = c.take<double>(2 * n_pts); d_val = c.take<double>(2 * n_pts); d_q = c.take<double>(2 * n_q); d_out = c.take<double>(2 * n_q);
+            d_simp = c.take<int32_t>(3 * n_simp); d_t = c.take<Simp>(n_simp); d_loc = c.take<int32_t>(n_q);
+            d_near = c.take<int32_t>(n_q); d_sx = c.take<int32_t>(n_q); d_dbt = c.take<int32_t>(n_q); d_list = c.take<int32_t>(n_q); d_nlist = c.take<int32_t>(1);
+            d_cnt = c.take<int32_t>(kGrid * kGrid + 1); d_start = c.take<int32_t>(kGrid * kGrid + 1); d_ids = c.take<int32_t>(grid_cap);
+        }))
+        return rc;
     bool use_grid = false;
     GridGeo geo{0.0, 0.0, 0.0, 0.0};
-    if ((rc = pool_reserve(device, need, &blk))) { (void)hipSetDevice(prev); return rc; }
-    {
-        Carver cv(blk);
-        d_pts = cv.take<double>(2 * n_pts); d_val = cv.take<double>(2 * n_pts); d_q = cv.take<double>(2 * n_q); d_out = cv.take<double>(2 * n_q);
-        d_simp = cv.take<int32_t>(3 * n_simp); d_t = cv.take<Simp>(n_simp); d_loc = cv.take<int32_t>(n_q);
-        d_near = cv.take<int32_t>(n_q); d_sx = cv.take<int32_t>(n_q); d_dbt = cv.take<int32_t>(n_q); d_list = cv.take<int32_t>(n_q); d_nlist = cv.take<int32_t>(1);
-        d_cnt = cv.take<int32_t>(kGrid * kGrid + 1); d_start = cv.take<int32_t>(kGrid * kGrid + 1); d_ids = cv.take<int32_t>(grid_cap);
-    }
     {   // grid geometry: the bounding box of the key points
-        double x_lo = pts[0], x_hi = pts[0], y_lo = pts[1], y_hi = pts[1];
-        for (int64_t k = 1; k < n_pts; ++k) {
-            x_lo = fmin(x_lo, pts[2 * k]); x_hi = fmax(x_hi, pts[2 * k]); y_lo = fmin(y_lo, pts[2 * k + 1]); y_hi = fmax(y_hi, pts[2 * k + 1]);
+        Box bx;
+        for (int64_t k = 0; k < n_pts; ++k) bx.add(pts[2 * k], pts[2 * k + 1]);
+        const double w = bx.x_hi - bx.x_lo, h = bx.y_hi - bx.y_lo;
+        if (getenv("SID_FG_NO_GRID") == nullptr && w > 0.0 && h > 0.0 && isfinite(w) && isfinite(h)) {
+            geo = GridGeo{bx.x_lo, bx.y_lo, (double)kGrid / w, (double)kGrid / h};
+            use_grid = true;
         }
-        const double w = x_hi - x_lo, h = y_hi - y_lo;
-        if (want_grid && w > 0.0 && h > 0.0 && isfinite(w) && isfinite(h)) { geo = GridGeo{x_lo, y_lo, (double)kGrid / w, (double)kGrid / h}; use_grid = true; }
     }
     HIP_TRY(hipMemcpyAsync(d_pts, pts, sizeof(double) * 2 * n_pts, hipMemcpyHostToDevice, 0));
     HIP_TRY(hipMemcpyAsync(d_val, values, sizeof(double) * 2 * n_pts, hipMemcpyHostToDevice, 0));
-    if (q) HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
     HIP_TRY(hipMemcpyAsync(d_simp, simplices, sizeof(int32_t) * 3 * n_simp, hipMemcpyHostToDevice, 0));
     hipLaunchKernelGGL(k_transform, dim3((unsigned)((n_simp + 255) / 256)), dim3(256), 0, 0, d_pts, d_simp, n_simp, d_t);
-    {
-        const unsigned qb = (unsigned)((n_q + 255) / 256), sb = (unsigned)((n_simp + 255) / 256);
-        if (use_grid) {
-            // bucket lists: count, prefix sums, fill; the total decides whether they fit (one 4-byte read-back)
-            int32_t total = 0;
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
-            hipLaunchKernelGGL(k_grid_build<0>, dim3(sb), dim3(256), 0, 0, d_pts, d_simp, d_t, n_simp, geo, d_cnt, d_start, d_ids, grid_cap);
-            hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
-            HIP_TRY(hipMemcpy(&total, d_start + kGrid * kGrid, sizeof total, hipMemcpyDeviceToHost));
-            if ((int64_t)total <= grid_cap) hipLaunchKernelGGL(k_grid_build<1>, dim3(sb), dim3(256), 0, 0, d_pts, d_simp, d_t, n_simp, geo, d_cnt, d_start, d_ids, grid_cap);
-            else use_grid = false;
-        }
-        if (use_grid) {
-            hipLaunchKernelGGL(k_locate_grid, dim3(qb), dim3(256), 0, 0, d_t, d_start, d_ids, geo, d_q, n_q, d_loc, d_near);
-        } else {
-            unsigned ychunks = qb >= 2048 ? 1u : (2048u + qb - 1) / qb;                 // aim at >= 2048 blocks
-            const int64_t tiles = (n_simp + kTile - 1) / kTile;
-            if ((int64_t)ychunks > tiles) ychunks = (unsigned)tiles;
-            const int64_t chunk = ((tiles + ychunks - 1) / ychunks) * kTile;
-            ychunks = (unsigned)((n_simp + chunk - 1) / chunk);
-            HIP_TRY(hipMemsetAsync(d_loc, 0x7f, sizeof(int32_t) * n_q, 0));             // 0x7f7f7f7f: above any index
-            HIP_TRY(hipMemsetAsync(d_near, 0, sizeof(int32_t) * n_q, 0));
-            hipLaunchKernelGGL(k_locate, dim3(qb, ychunks), dim3(256), 0, 0, d_t, n_simp, chunk, d_q, n_q, d_loc, d_near);
-        }
-        HIP_TRY(hipMemsetAsync(d_nlist, 0, sizeof(int32_t), 0));
-        hipLaunchKernelGGL(k_eval, dim3(qb), dim3(256), 0, 0, d_t, d_loc, d_near, d_val, d_q, n_q, d_out, d_sx, d_dbt, d_list, d_nlist);
-        // (the number of flagged queries is only known on the device: enough wavefronts for a few thousand of them at once,
-        // each taking every 4096th entry of the list)
-        hipLaunchKernelGGL(k_resolve, dim3(1024), dim3(256), 0, 0, d_t, n_simp, d_val, d_q, d_list, d_nlist, d_out, d_sx, d_dbt,
-                           use_grid ? d_start : nullptr, use_grid ? d_ids : nullptr, geo);
+    const unsigned qb = (unsigned)((n_q + 255) / 256), sb = (unsigned)((n_simp + 255) / 256);
+    if (use_grid) {
+        // bucket lists: count, prefix sums, fill; the total decides whether they fit (one 4-byte read-back)
+        int32_t total = 0;
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
+        hipLaunchKernelGGL(k_grid_build<0>, dim3(sb), dim3(256), 0, 0, d_pts, d_simp, d_t, n_simp, geo, d_cnt, d_start, d_ids, grid_cap);
+        hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
+        HIP_TRY(hipMemcpy(&total, d_start + kGrid * kGrid, sizeof total, hipMemcpyDeviceToHost));
+        if ((int64_t)total <= grid_cap) hipLaunchKernelGGL(k_grid_build<1>, dim3(sb), dim3(256), 0, 0, d_pts, d_simp, d_t, n_simp, geo, d_cnt, d_start, d_ids, grid_cap);
+        else use_grid = false;
     }
+    if (use_grid) {
+        hipLaunchKernelGGL(k_locate_grid, dim3(qb), dim3(256), 0, 0, d_t, d_start, d_ids, geo, d_q, n_q, d_loc, d_near);
+    } else {
+        unsigned ychunks = qb >= 2048 ? 1u : (2048u + qb - 1) / qb;                 // aim at >= 2048 blocks
+        const int64_t tiles = (n_simp + kTile - 1) / kTile;
+        if ((int64_t)ychunks > tiles) ychunks = (unsigned)tiles;
+        const int64_t chunk = ((tiles + ychunks - 1) / ychunks) * kTile;
+        ychunks = (unsigned)((n_simp + chunk - 1) / chunk);
+        HIP_TRY(hipMemsetAsync(d_loc, 0x7f, sizeof(int32_t) * n_q, 0));             // 0x7f7f7f7f: above any index
+        HIP_TRY(hipMemsetAsync(d_near, 0, sizeof(int32_t) * n_q, 0));
+        hipLaunchKernelGGL(k_locate, dim3(qb, ychunks), dim3(256), 0, 0, d_t, n_simp, chunk, d_q, n_q, d_loc, d_near);
+    }
+    HIP_TRY(hipMemsetAsync(d_nlist, 0, sizeof(int32_t), 0));
+    hipLaunchKernelGGL(k_eval, dim3(qb), dim3(256), 0, 0, d_t, d_loc, d_near, d_val, d_q, n_q, d_out, d_sx, d_dbt, d_list, d_nlist);
+    // (the number of flagged queries is only known on the device: enough wavefronts for a few thousand of them at once,
+    // each taking every 4096th entry of the list)
+    hipLaunchKernelGGL(k_resolve, dim3(1024), dim3(256), 0, 0, d_t, n_simp, d_val, d_q, d_list, d_nlist, d_out, d_sx, d_dbt,
+                       use_grid ? d_start : nullptr, use_grid ? d_ids : nullptr, geo);
     HIP_TRY(hipGetLastError());
     if (simplex) HIP_TRY(hipMemcpyAsync(simplex, d_sx, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, 0));
     if (doubt) HIP_TRY(hipMemcpyAsync(doubt, d_dbt, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, 0));
     HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 2 * n_q, hipMemcpyDeviceToHost));    // (synchronous: the host arrays are the caller's)
     HIP_TRY(hipStreamSynchronize(0));
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    s.done();
+    return SID_PM_OK;
 }
 
-static int nearest_dist_impl(int device, const double *seeds, int64_t n_seeds, const double *q, int64_t n_q, double *dist, int64_t qcols);
+namespace {
+
+// The buckets of the seeds d_s (bounding box `bx`) that k_nearest_grid and k_knn_grid walk: geometry, margin, and the count,
+// prefix sums and fill queued on the null stream.  *used = false and nothing queued where the buckets do not pay or cannot
+// be built: fewer than 256 seeds, a seed that is not finite, a box without an area (SID_FG_NO_GRID=1: never; A/B runs and the
+// parity test of both).
+struct SeedGrid { GridGeo g; double wx, wy, margin; };
+int build_seed_buckets(const Box &bx, bool finite, const double *d_s, int64_t ns, int32_t *d_cnt, int32_t *d_start, int32_t *d_ids,
+                       SeedGrid &sg, bool *used)
+{
+    const double w = bx.x_hi - bx.x_lo, h = bx.y_hi - bx.y_lo;
+    *used = getenv("SID_FG_NO_GRID") == nullptr && ns >= 256 && finite && w > 0.0 && h > 0.0 && isfinite(w) && isfinite(h);
+    if (!*used) return SID_PM_OK;
+    sg.g = GridGeo{bx.x_lo, bx.y_lo, (double)kGrid / w, (double)kGrid / h};
+    sg.wx = w / kGrid; sg.wy = h / kGrid;
+    // rounding of (v - v0) * inv in cell_of moves a seed by at most a few ulp of the box across a cell border
+    sg.margin = 1e-9 * (w + h) + 1e-12 * (fabs(bx.x_lo) + fabs(bx.x_hi) + fabs(bx.y_lo) + fabs(bx.y_hi));
+    const unsigned nb = (unsigned)((ns + 255) / 256);
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
+    hipLaunchKernelGGL(k_seed_bin<0>, dim3(nb), dim3(256), 0, 0, d_s, ns, sg.g, d_cnt, (const int32_t *)nullptr, (int32_t *)nullptr);
+    hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
+    hipLaunchKernelGGL(k_seed_bin<1>, dim3(nb), dim3(256), 0, 0, d_s, ns, sg.g, d_cnt, d_start, d_ids);
+    return SID_PM_OK;
+}
+
+// q == nullptr: the queries are the pixels (row, column) of an image with `qcols` columns
+int nearest_dist_impl(int device, const double *seeds, int64_t n_seeds, const double *q, int64_t n_q, double *dist, int64_t qcols)
+{
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    double *d_s, *d_q, *d_d;
+    int32_t *d_cnt, *d_start, *d_ids;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            d_s = c.take<double>(2 * n_seeds); d_q = c.take<double>(2 * n_q, q != nullptr); d_d = c.take<double>(n_q);
+            d_cnt = c.take<int32_t>(kGrid * kGrid + 1); d_start = c.take<int32_t>(kGrid * kGrid + 1); d_ids = c.take<int32_t>(n_seeds);
+        }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_s, seeds, sizeof(double) * 2 * n_seeds, hipMemcpyHostToDevice, 0));
+    if (q) HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
+    // bounding box of the seeds (host: they are host arrays)
+    Box bx;
+    bool finite = true, grid = false;
+    for (int64_t k = 0; k < n_seeds; ++k) {
+        finite = finite && isfinite(seeds[2 * k]) && isfinite(seeds[2 * k + 1]);
+        bx.add(seeds[2 * k], seeds[2 * k + 1]);
+    }
+    SeedGrid sg;
+    if (int rc = build_seed_buckets(bx, finite, d_s, n_seeds, d_cnt, d_start, d_ids, sg, &grid)) return rc;
+    const dim3 blocks((unsigned)((n_q + 255) / 256));
+    if (grid) hipLaunchKernelGGL(k_nearest_grid, blocks, dim3(256), 0, 0, d_s, d_start, d_ids, sg.g, sg.wx, sg.wy, sg.margin, (const double *)d_q, n_q, d_d, qcols);
+    else hipLaunchKernelGGL(k_nearest, blocks, dim3(256), 0, 0, d_s, n_seeds, (const double *)d_q, n_q, d_d, qcols);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(dist, d_d, sizeof(double) * n_q, hipMemcpyDeviceToHost));
+    s.done();
+    return SID_PM_OK;
+}
+
+}  // namespace
 
 SID_EXPORT int sid_fg_nearest_dist(int device, const double *seeds, int64_t n_seeds, const double *q, int64_t n_q, double *dist)
 {
@@ -599,59 +595,50 @@ SID_EXPORT int sid_fg_distance_image(int device, const double *seeds, int64_t n_
     return nearest_dist_impl(device, seeds, n_seeds, nullptr, rows * cols, dist, cols);
 }
 
-// q == nullptr: the queries are the pixels (row, column) of an image with `qcols` columns
-static int nearest_dist_impl(int device, const double *seeds, int64_t n_seeds, const double *q, int64_t n_q, double *dist, int64_t qcols)
+namespace {
+
+// sid_fg_knn on a device, over the usable seeds; count and index are never null here (index may be: the device's own is used)
+int knn_on_device(int device, const double *seeds, const double *values, int64_t n_use, const Box &bx, const double *q, int64_t n_q,
+                  int k, double m2, double *out, int32_t *count, int32_t *index)
 {
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    unsigned char *blk = nullptr;
-    double *d_s = nullptr, *d_q = nullptr, *d_d = nullptr;
-    int32_t *d_cnt = nullptr, *d_start = nullptr, *d_ids = nullptr;
-    if ((rc = pool_reserve(device, up(sizeof(double) * 2 * n_seeds) + up(sizeof(double) * 2 * (q ? n_q : 1)) + up(sizeof(double) * n_q) +
-                                   up(sizeof(int32_t) * (kGrid * kGrid + 1)) * 2 + up(sizeof(int32_t) * n_seeds), &blk))) { (void)hipSetDevice(prev); return rc; }
-    {
-        Carver cv(blk);
-        d_s = cv.take<double>(2 * n_seeds); d_q = cv.take<double>(2 * (q ? n_q : 1)); d_d = cv.take<double>(n_q);
-        if (!q) d_q = nullptr;
-        d_cnt = cv.take<int32_t>(kGrid * kGrid + 1); d_start = cv.take<int32_t>(kGrid * kGrid + 1); d_ids = cv.take<int32_t>(n_seeds);
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    if (n_use == 0) {                                                   // nothing to search: every result is empty
+        for (int64_t i = 0; i < n_q; ++i) { out[2 * i] = NAN; out[2 * i + 1] = NAN; count[i] = 0; for (int j = 0; j < k; ++j) index[i * k + j] = -1; }
+        s.done();
+        return SID_PM_OK;
     }
-    HIP_TRY(hipMemcpyAsync(d_s, seeds, sizeof(double) * 2 * n_seeds, hipMemcpyHostToDevice, 0));
-    if (q) HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
-    {
-        // bounding box of the seeds (host: they are host arrays); the buckets pay from a few hundred seeds on, and need finite
-        // coordinates and a box with an area (SID_FG_NO_GRID=1: brute force always; A/B runs and the parity test of both)
-        double x_lo = INFINITY, x_hi = -INFINITY, y_lo = INFINITY, y_hi = -INFINITY;
-        bool finite = true;
-        for (int64_t k = 0; k < n_seeds; ++k) {
-            const double sx = seeds[2 * k], sy = seeds[2 * k + 1];
-            finite = finite && isfinite(sx) && isfinite(sy);
-            x_lo = fmin(x_lo, sx); x_hi = fmax(x_hi, sx); y_lo = fmin(y_lo, sy); y_hi = fmax(y_hi, sy);
-        }
-        const double w = x_hi - x_lo, h = y_hi - y_lo;
-        if (getenv("SID_FG_NO_GRID") == nullptr && n_seeds >= 256 && finite && w > 0.0 && h > 0.0 && isfinite(w) && isfinite(h)) {
-            const GridGeo geo{x_lo, y_lo, (double)kGrid / w, (double)kGrid / h};
-            // rounding of (v - v0) * inv in cell_of moves a seed by at most a few ulp of the box across a cell border
-            const double margin = 1e-9 * (w + h) + 1e-12 * (fabs(x_lo) + fabs(x_hi) + fabs(y_lo) + fabs(y_hi));
-            const unsigned nb = (unsigned)((n_seeds + 255) / 256);
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
-            hipLaunchKernelGGL(k_seed_bin<0>, dim3(nb), dim3(256), 0, 0, d_s, n_seeds, geo, d_cnt, (const int32_t *)nullptr, (int32_t *)nullptr);
-            hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
-            hipLaunchKernelGGL(k_seed_bin<1>, dim3(nb), dim3(256), 0, 0, d_s, n_seeds, geo, d_cnt, d_start, d_ids);
-            hipLaunchKernelGGL(k_nearest_grid, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, 0, d_s, d_start, d_ids, geo, w / kGrid, h / kGrid, margin,
-                               (const double *)d_q, n_q, d_d, qcols);
-        } else {
-            hipLaunchKernelGGL(k_nearest, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, 0, d_s, n_seeds, (const double *)d_q, n_q, d_d, qcols);
-        }
-    }
+    double *d_s, *d_v, *d_q, *d_out;
+    int32_t *d_count, *d_index, *d_cnt, *d_start, *d_ids;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            d_s = c.take<double>(2 * n_use); d_v = c.take<double>(2 * n_use); d_q = c.take<double>(2 * n_q); d_out = c.take<double>(2 * n_q);
+            d_count = c.take<int32_t>(n_q); d_index = c.take<int32_t>((size_t)n_q * k);
+            d_cnt = c.take<int32_t>(kGrid * kGrid + 1); d_start = c.take<int32_t>(kGrid * kGrid + 1); d_ids = c.take<int32_t>(n_use);
+        }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_s, seeds, sizeof(double) * 2 * n_use, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(d_v, values, sizeof(double) * 2 * n_use, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
+    KnnArgs a{};
+    a.seeds = d_s; a.values = d_v; a.q = d_q; a.ns = n_use; a.nq = n_q; a.k = k; a.m2 = m2; a.out = d_out; a.count = d_count; a.index = d_index;
+    SeedGrid sg;
+    bool grid = false;
+    if (int rc = build_seed_buckets(bx, true, d_s, n_use, d_cnt, d_start, d_ids, sg, &grid)) return rc;
+    if (grid) { a.g = sg.g; a.wx = sg.wx; a.wy = sg.wy; a.margin = sg.margin; a.start = d_start; a.ids = d_ids; }
+    if (k == 1) knn_launch<1>(a);
+    else if (k <= 4) knn_launch<4>(a);
+    else if (k <= 8) knn_launch<8>(a);
+    else knn_launch<16>(a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(dist, d_d, sizeof(double) * n_q, hipMemcpyDeviceToHost));
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    HIP_TRY(hipMemcpyAsync(count, d_count, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, 0));
+    if (index) HIP_TRY(hipMemcpyAsync(index, d_index, sizeof(int32_t) * n_q * k, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 2 * n_q, hipMemcpyDeviceToHost));   // (synchronous: the host arrays are the caller's)
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
 }
+
+}  // namespace
 
 // The k nearest usable seeds of every query and the component-wise median of their values (sid_fg.h).
 SID_EXPORT int sid_fg_knn(int device, const double *seeds, int64_t n_seeds, const double *values, const double *q, int64_t n_q,
@@ -666,11 +653,11 @@ SID_EXPORT int sid_fg_knn(int device, const double *seeds, int64_t n_seeds, cons
     // The usable seeds (finite coordinates and values), their bounding box, and - only when some seed is not usable - a compacted
     // copy in the same order with the map back to the caller's indices: no other seed reaches a kernel or a bucket.
     int64_t n_use = 0;
-    double x_lo = INFINITY, x_hi = -INFINITY, y_lo = INFINITY, y_hi = -INFINITY;
+    Box bx;
     for (int64_t s = 0; s < n_seeds; ++s)
         if (isfinite(seeds[2 * s]) && isfinite(seeds[2 * s + 1]) && isfinite(values[2 * s]) && isfinite(values[2 * s + 1])) {
             ++n_use;
-            x_lo = fmin(x_lo, seeds[2 * s]); x_hi = fmax(x_hi, seeds[2 * s]); y_lo = fmin(y_lo, seeds[2 * s + 1]); y_hi = fmax(y_hi, seeds[2 * s + 1]);
+            bx.add(seeds[2 * s], seeds[2 * s + 1]);
         }
     std::vector<double> cs, cv;
     std::vector<int32_t> map;
@@ -689,65 +676,12 @@ SID_EXPORT int sid_fg_knn(int device, const double *seeds, int64_t n_seeds, cons
         if (!count) { h_count.resize(n_q); count = h_count.data(); }
         if (!index && (device == -1 || n_use == 0)) { h_index.resize((size_t)n_q * k); index = h_index.data(); }
     } catch (...) { return fail(SID_PM_ERR_NOMEM, "host allocation failed"); }
-    int prev = 0;
-    int rc = SID_PM_OK;
     if (device == -1) {
         for (int64_t i = 0; i < n_q; ++i) sid_knn::brute(seeds, values, n_use, q[2 * i], q[2 * i + 1], k, m2, out + 2 * i, count + i, index + i * k);
-    } else {
-        if (int rc0 = pick_device(device, prev)) return rc0;
-        if (n_use == 0) {                                               // nothing to search: every result is empty
-            for (int64_t i = 0; i < n_q; ++i) { out[2 * i] = NAN; out[2 * i + 1] = NAN; count[i] = 0; for (int j = 0; j < k; ++j) index[i * k + j] = -1; }
-            (void)hipSetDevice(prev);
-            return SID_PM_OK;
-        }
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        unsigned char *blk = nullptr;
-        KnnArgs a{};
-        double *d_s = nullptr, *d_v = nullptr, *d_q = nullptr, *d_out = nullptr;
-        int32_t *d_count = nullptr, *d_index = nullptr, *d_cnt = nullptr, *d_start = nullptr, *d_ids = nullptr;
-        const double w = x_hi - x_lo, h = y_hi - y_lo;
-        const bool grid = getenv("SID_FG_NO_GRID") == nullptr && n_use >= 256 && w > 0.0 && h > 0.0 && isfinite(w) && isfinite(h);
-        if ((rc = pool_reserve(device, up(sizeof(double) * 2 * n_use) * 2 + up(sizeof(double) * 2 * n_q) * 2 + up(sizeof(int32_t) * n_q) +
-                                       up(sizeof(int32_t) * n_q * k) + up(sizeof(int32_t) * (kGrid * kGrid + 1)) * 2 + up(sizeof(int32_t) * n_use), &blk))) {
-            (void)hipSetDevice(prev);
-            return rc;
-        }
-        {
-            Carver cv2(blk);
-            d_s = cv2.take<double>(2 * n_use); d_v = cv2.take<double>(2 * n_use); d_q = cv2.take<double>(2 * n_q); d_out = cv2.take<double>(2 * n_q);
-            d_count = cv2.take<int32_t>(n_q); d_index = cv2.take<int32_t>((size_t)n_q * k);
-            d_cnt = cv2.take<int32_t>(kGrid * kGrid + 1); d_start = cv2.take<int32_t>(kGrid * kGrid + 1); d_ids = cv2.take<int32_t>(n_use);
-        }
-        HIP_TRY(hipMemcpyAsync(d_s, seeds, sizeof(double) * 2 * n_use, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(d_v, values, sizeof(double) * 2 * n_use, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * 2 * n_q, hipMemcpyHostToDevice, 0));
-        a.seeds = d_s; a.values = d_v; a.q = d_q; a.ns = n_use; a.nq = n_q; a.k = k; a.m2 = m2; a.out = d_out; a.count = d_count; a.index = d_index;
-        if (grid) {
-            // the buckets of sid_fg_nearest_dist: same geometry, same binning kernels, same margin
-            const unsigned nb = (unsigned)((n_use + 255) / 256);
-            a.g = GridGeo{x_lo, y_lo, (double)kGrid / w, (double)kGrid / h};
-            a.wx = w / kGrid; a.wy = h / kGrid;
-            a.margin = 1e-9 * (w + h) + 1e-12 * (fabs(x_lo) + fabs(x_hi) + fabs(y_lo) + fabs(y_hi));
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
-            hipLaunchKernelGGL(k_seed_bin<0>, dim3(nb), dim3(256), 0, 0, d_s, n_use, a.g, d_cnt, (const int32_t *)nullptr, (int32_t *)nullptr);
-            hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
-            hipLaunchKernelGGL(k_seed_bin<1>, dim3(nb), dim3(256), 0, 0, d_s, n_use, a.g, d_cnt, d_start, d_ids);
-            a.start = d_start; a.ids = d_ids;
-        }
-        if (k == 1) knn_launch<1>(a);
-        else if (k <= 4) knn_launch<4>(a);
-        else if (k <= 8) knn_launch<8>(a);
-        else knn_launch<16>(a);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(count, d_count, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, 0));
-        if (index) HIP_TRY(hipMemcpyAsync(index, d_index, sizeof(int32_t) * n_q * k, hipMemcpyDeviceToHost, 0));
-        HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 2 * n_q, hipMemcpyDeviceToHost));   // (synchronous: the host arrays are the caller's)
-        HIP_TRY(hipStreamSynchronize(0));
+    } else if (int rc = knn_on_device(device, seeds, values, n_use, bx, q, n_q, k, m2, out, count, index)) {
+        return rc;
     }
     if (index && !map.empty())                                          // compacted indices -> the caller's
         for (int64_t e = 0; e < n_q * k; ++e) if (index[e] >= 0) index[e] = map[index[e]];
-done:
-    if (device != -1) (void)hipSetDevice(prev);
-    return rc;
+    return SID_PM_OK;
 }

@@ -18,29 +18,17 @@
 // distance, then by the smaller index.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <algorithm>
-#include <mutex>
 #include <stdlib.h>
 
 #include "../../include/sid_ft.h"
-#include "../../include/sid_pm.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr int64_t kMaxTrain = (int64_t)1 << 22;             // index bits of the key
-
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 __device__ __forceinline__ void push(uint32_t &k1, uint32_t &k2, uint32_t key)
 {
@@ -242,7 +230,6 @@ MfmaPlan plan_mfma(int64_t n1, int64_t n2)
     want = std::min<int64_t>(want, batches);
     const int64_t per = (batches + want - 1) / want;
     P.chunk = (int)(per * kTB); P.nchunks = (int)((batches + per - 1) / per);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     P.off_e1 = up(sizeof(uint32_t) * 2 * (size_t)std::max<int64_t>(n1, 1) * P.nchunks);
     P.off_e2 = P.off_e1 + (size_t)P.n1pad * 256;
     P.off_c = P.off_e2 + (size_t)P.n2pad * 256;
@@ -308,23 +295,12 @@ SID_EXPORT int sid_ft_knn2_device(const uint8_t *d_desc1, int64_t n1, const uint
     return SID_PM_OK;
 }
 
-// device scratch of sid_ft_knn2: one grow-only block per device (sid_ft_release frees it)
-static std::mutex g_ft_mu[16];
-static unsigned char *g_ft_pool[16] = {nullptr};
-static size_t g_ft_cap[16] = {0};
+// Device scratch of sid_ft_knn2: one grow-only block per device, kept between calls (five hipMalloc / hipFree cost about as much
+// as the matching of the reference notebook's 24 000 x 23 000 case; sid_ft_release frees it).  One mutex per device: calls on one
+// device are serialised, calls on different devices run side by side.
+static DevicePool<NoExtra, true> g_pool;
 
-SID_EXPORT int sid_ft_release(int device)
-{
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    for (int d = 0; d < 16; ++d) {
-        if (device >= 0 && d != (device & 15)) continue;
-        std::lock_guard<std::mutex> lock(g_ft_mu[d]);
-        if (g_ft_pool[d]) { (void)hipSetDevice(d); (void)hipFree(g_ft_pool[d]); g_ft_pool[d] = nullptr; g_ft_cap[d] = 0; }
-    }
-    (void)hipSetDevice(prev);
-    return SID_PM_OK;
-}
+SID_EXPORT int sid_ft_release(int device) { return g_pool.release(device); }
 
 SID_EXPORT int sid_ft_knn2(int device, const uint8_t *desc1, int64_t n1, const uint8_t *desc2, int64_t n2,
                            int32_t *idx, int32_t *dist)
@@ -332,46 +308,26 @@ SID_EXPORT int sid_ft_knn2(int device, const uint8_t *desc1, int64_t n1, const u
     if (n1 < 0 || n2 < 0) return fail(SID_PM_ERR_ARG, "negative descriptor count");
     if (n1 == 0) return SID_PM_OK;
     if (!desc1 || !idx || !dist || (n2 > 0 && !desc2)) return fail(SID_PM_ERR_ARG, "null pointer");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SID_PM_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(SID_PM_ERR_ARG, "device %d out of range", device);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
-    // device scratch: one grow-only block per device, kept between calls (five hipMalloc / hipFree cost about as much as
-    // the matching of the reference notebook's 24 000 x 23 000 case); calls on one device are serialised by its mutex
-    std::mutex *mu = g_ft_mu;
-    unsigned char **pool = g_ft_pool;
-    size_t *pool_cap = g_ft_cap;
-    std::lock_guard<std::mutex> lock(mu[device & 15]);
-    hipError_t e = hipSuccess;
-    auto step = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t s1 = up((size_t)n1 * SID_FT_DESC_BYTES), s2 = up((size_t)std::max<int64_t>(n2, 1) * SID_FT_DESC_BYTES);
-    const size_t sw = up((size_t)sid_ft_workspace_bytes(n1, n2)), so = up(sizeof(int32_t) * 2 * (size_t)n1);
-    const size_t need = s1 + s2 + sw + 2 * so;
-    if (pool_cap[device & 15] < need) {
-        if (pool[device & 15]) (void)hipFree(pool[device & 15]);
-        pool[device & 15] = nullptr; pool_cap[device & 15] = 0;
-        step(hipMalloc(reinterpret_cast<void **>(&pool[device & 15]), need + need / 4));
-        if (e == hipSuccess) pool_cap[device & 15] = need + need / 4;
-    }
-    uint8_t *b1 = pool[device & 15], *b2 = b1 ? b1 + s1 : nullptr, *ws = b1 ? b2 + s2 : nullptr;
-    int32_t *bi = b1 ? reinterpret_cast<int32_t *>(ws + sw) : nullptr, *bd = b1 ? reinterpret_cast<int32_t *>(ws + sw + so) : nullptr;
-    if (e == hipSuccess) {
-        step(hipMemcpyAsync(b1, desc1, (size_t)n1 * SID_FT_DESC_BYTES, hipMemcpyHostToDevice, nullptr));
-        if (n2 > 0) step(hipMemcpyAsync(b2, desc2, (size_t)n2 * SID_FT_DESC_BYTES, hipMemcpyHostToDevice, nullptr));
-    }
-    int rc = SID_PM_OK;
-    if (e == hipSuccess) rc = sid_ft_knn2_device(b1, n1, b2, n2, bi, bd, ws, nullptr);
-    if (e == hipSuccess && rc == SID_PM_OK) {
-        step(hipMemcpyAsync(idx, bi, sizeof(int32_t) * 2 * (size_t)n1, hipMemcpyDeviceToHost, nullptr));
-        step(hipMemcpyAsync(dist, bd, sizeof(int32_t) * 2 * (size_t)n1, hipMemcpyDeviceToHost, nullptr));
-        step(hipStreamSynchronize(nullptr));
-    } else {
-        (void)hipStreamSynchronize(nullptr);                           // (nothing of a failed call stays in flight in the pool)
-    }
-    (void)hipSetDevice(prev);
-    if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "sid_ft_knn2: %s", hipGetErrorString(e));
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device))
+        return s.dev.visible < 1 ? fail(SID_PM_ERR_NODEVICE, "no HIP device visible") : fail(SID_PM_ERR_ARG, "device %d out of range", device);
+    const size_t b1 = (size_t)n1 * SID_FT_DESC_BYTES, b2 = (size_t)n2 * SID_FT_DESC_BYTES, bo = sizeof(int32_t) * 2 * (size_t)n1;
+    uint8_t *d1, *d2, *ws;
+    int32_t *di, *dd;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            d1 = c.take<uint8_t>(b1);
+            d2 = c.take<uint8_t>(std::max<size_t>(b2, SID_FT_DESC_BYTES));      // (an empty train set: sized, never read)
+            ws = c.take<uint8_t>((size_t)sid_ft_workspace_bytes(n1, n2));
+            di = c.take<int32_t>(2 * (size_t)n1);
+            dd = c.take<int32_t>(2 * (size_t)n1);
+        }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d1, desc1, b1, hipMemcpyHostToDevice, nullptr));
+    if (n2 > 0) HIP_TRY(hipMemcpyAsync(d2, desc2, b2, hipMemcpyHostToDevice, nullptr));
+    if (int rc = sid_ft_knn2_device(d1, n1, d2, n2, di, dd, ws, nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(idx, di, bo, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(dist, dd, bo, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    s.done();
+    return SID_PM_OK;
 }

@@ -12,18 +12,14 @@
 //                      operations.  -ffp-contract=off: every product and sum is a rounding of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 #include <limits.h>
 #include <algorithm>
 
 #include "../../include/sid_mask.h"
-#include "../../include/sid_pm.h"
+#include "host_util.h"
 #include "pm_large.h"
 #include "prep_pixel.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
 
@@ -32,13 +28,6 @@ constexpr int kRows = 64;                // output rows per workgroup
 constexpr int kTileCap = 4096;           // float64 coefficients staged per workgroup at the most (32 KiB)
 constexpr int kOutside = INT_MIN;        // first tap of a row / column whose coordinate lies outside the raster
 constexpr size_t kRowBytes = kRows * 4 * sizeof(double) + kRows * sizeof(int);   // LDS in front of the coefficient patch
-
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 __global__ __launch_bounds__(kThreads) void clip_max3_kernel(const uint8_t *wm, int h, int w, int64_t stride, uint8_t *out)
 {
@@ -215,22 +204,6 @@ int check_plane(const void *p, int64_t cols, int64_t stride, const char *what)
     return SID_PM_OK;
 }
 
-// launches go to the device that holds the output (the null stream belongs to the CURRENT device)
-struct DeviceOf {
-    int prev = -1;
-    explicit DeviceOf(const void *p)
-    {
-        hipPointerAttribute_t at;
-        int cur = 0; (void)hipGetDevice(&cur);
-        if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device != cur) {
-            prev = cur; (void)hipSetDevice(at.device);
-        } else (void)hipGetLastError();                      // (a pointer HIP does not know leaves an error behind)
-    }
-    ~DeviceOf() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // coefficients the taps of `n` consecutive output indices reach along an axis with zoom step z, at the most
 long long taps_bound(int n, double z) { return (long long)ceil((double)(n - 1) * z) + 5; }
 
@@ -278,7 +251,7 @@ int run(const uint8_t *d_wm, int64_t h, int64_t w, int64_t wm_stride, int64_t H,
     const int px = vec ? 4 : 1;
     size_t lds = 0;
     if (d_wm) {
-        const size_t plane = up256((size_t)h * (size_t)w * sizeof(double));
+        const size_t plane = up((size_t)h * (size_t)w * sizeof(double));
         double *buf0 = static_cast<double *>(d_work), *buf1 = reinterpret_cast<double *>(static_cast<char *>(d_work) + plane);
         uint8_t *wmf = reinterpret_cast<uint8_t *>(static_cast<char *>(d_work) + 2 * plane);
         const int64_t blocks = std::min<int64_t>((h * w + kThreads - 1) / kThreads, 2048);
@@ -296,9 +269,7 @@ int run(const uint8_t *d_wm, int64_t h, int64_t w, int64_t wm_stride, int64_t H,
     const dim3 grid((unsigned)((W + (int64_t)kThreads * px - 1) / ((int64_t)kThreads * px)), (unsigned)((H + kRows - 1) / kRows));
     if (vec) launch_zoom<4>(d_img != nullptr, d_wm != nullptr, grid, lds, st, Z, d_img, img_stride, dB != 0, d_ia, ia_stride, hh_factor, d_mask, mask_stride, d_wmz, wmz_stride);
     else launch_zoom<1>(d_img != nullptr, d_wm != nullptr, grid, lds, st, Z, d_img, img_stride, dB != 0, d_ia, ia_stride, hh_factor, d_mask, mask_stride, d_wmz, wmz_stride);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "zoom: %s", hipGetErrorString(e));
-    return SID_PM_OK;
+    return launched("zoom");
 }
 
 }  // namespace
@@ -308,7 +279,7 @@ SID_EXPORT const char *sid_mask_last_error(void) { return g_err; }
 SID_EXPORT int64_t sid_mask_workspace_bytes(int64_t h, int64_t w)
 {
     if (h < 2 || w < 2 || h > INT_MAX || w > INT_MAX || h * w > (int64_t)1 << 40) return 0;
-    return (int64_t)(2 * up256((size_t)h * (size_t)w * sizeof(double)) + up256((size_t)h * (size_t)w));
+    return (int64_t)(2 * up((size_t)h * (size_t)w * sizeof(double)) + up((size_t)h * (size_t)w));
 }
 
 SID_EXPORT int sid_mask_landmask(const uint8_t *d_wm, int64_t h, int64_t w, int64_t wm_stride, int64_t H, int64_t W, void *d_work,

@@ -11,29 +11,18 @@
 // per image and is a small part of the feature-tracking + pattern-matching chain (tools/ftpm_bench.py).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
 #include <chrono>
-#include <mutex>
 
 #include "../../include/sid_orb.h"
-#include "../../include/sid_pm.h"
+#include "host_util.h"
 
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
 
 struct Cand { int32_t x, y; long long resp; };
 
@@ -542,11 +531,19 @@ hipError_t ws_reserve(OrbWs *w, size_t bytes)
     if (e == hipSuccess) w->cap = bytes;
     return e;
 }
-struct WsCarver {
-    unsigned char *base; size_t off = 0;
-    template <typename T> T *take(size_t n) { T *r = reinterpret_cast<T *>(base + off); off += (n * sizeof(T) + 255) / 256 * 256; return r; }
+// A call's hold on a workspace of its device: selected and acquired by the call, given back - stream drained, so that nothing of
+// the call is still in flight in a workspace that is free - and the previous device restored on every way out
+struct WsLease {
+    OrbWs *ws = nullptr;
+    int prev = 0;
+    explicit WsLease(int device) { (void)hipGetDevice(&prev); (void)hipSetDevice(device); ws = ws_acquire(device); }
+    ~WsLease()
+    {
+        if (ws) (void)hipStreamSynchronize(ws->stream);
+        ws_release(ws);
+        (void)hipSetDevice(prev);
+    }
 };
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -560,7 +557,6 @@ int detect_on_device(OrbWs *ws, const DevBufs &B, int64_t rows, int64_t cols, co
                      const std::vector<int> &lr, const std::vector<int> &lc, const std::vector<int> &want, unsigned int sel_cap,
                      float *xy, int32_t *meta, int64_t *response, uint8_t *desc, int64_t max_out, int64_t *total_out, bool *overflow)
 {
-    int rc = SID_PM_OK;
     hipStream_t st = ws->stream;
     const int L = P->n_levels, edge = P->edge_threshold, R = P->patch_size / 2;
     *overflow = false; *total_out = 0;
@@ -617,8 +613,7 @@ int detect_on_device(OrbWs *ws, const DevBufs &B, int64_t rows, int64_t cols, co
         }
         *total_out = n;
     }
-done:
-    return rc;
+    return SID_PM_OK;
 }
 
 SID_EXPORT const char *sid_orb_last_error(void) { return g_err; }
@@ -646,13 +641,10 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
     *n_out = 0;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
-    int prev = 0; (void)hipGetDevice(&prev); (void)hipSetDevice(device);
-    int rc = SID_PM_OK;
     const int L = P->n_levels, edge = P->edge_threshold, R = P->patch_size / 2;
     // SID_ORB_VERBOSE=1: wall-clock milliseconds per stage on stderr (synchronises after every stage)
     const bool verbose = getenv("SID_ORB_VERBOSE") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
-    OrbWs *ws = nullptr;
     hipStream_t st = nullptr;
     auto tick = [&](const char *what, int level) {
         if (!verbose) return;
@@ -687,19 +679,23 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
         }
         const size_t area0 = (size_t)rows * cols;
         const size_t nkp = (size_t)std::max<int64_t>(std::min<int64_t>((int64_t)P->n_features, max_out), 1);   // most key points of one level
-        ws = ws_acquire(device);
-        if (!ws) { rc = fail(SID_PM_ERR_NOMEM, "no detector workspace"); goto done; }
+        const WsLease lease(device);
+        OrbWs *ws = lease.ws;
+        if (!ws) return fail(SID_PM_ERR_NOMEM, "no detector workspace");
         st = ws->stream;
-        HIP_TRY(ws_reserve(ws, 3 * up256(area0) + up256((area0 / 4 + 16) * sizeof(Cand)) + up256((size_t)sel_cap * sizeof(Cand)) + up256(32 * 1024) +
-                               up256(nkp * 4 * sizeof(int32_t)) + up256(nkp * sizeof(int32_t)) + up256(nkp * 32) + 4 * 256 + up256(2048 * sizeof(unsigned int)) +
-                               up256(nkp * 2 * sizeof(float)) + up256(nkp * sizeof(long long)) + 256 + up256((size_t)sel_cap * sizeof(unsigned int))));
         {
-            WsCarver cv{ws->blk};
-            d_img0 = cv.take<uint8_t>(area0); d_lvl = cv.take<uint8_t>(area0); d_aux = cv.take<uint8_t>(area0);
-            d_cand = cv.take<Cand>(area0 / 4 + 16); d_sel = cv.take<Cand>(sel_cap); d_pat = cv.take<int8_t>(32 * 1024);
-            d_kp = cv.take<int32_t>(nkp * 4); d_dir = cv.take<int32_t>(nkp); d_desc = cv.take<uint8_t>(nkp * 32);
-            d_count = cv.take<unsigned int>(1); d_dirs = cv.take<int32_t>(64); d_hist = cv.take<unsigned int>(2048);
-            d_xy = cv.take<float>(nkp * 2); d_resp = cv.take<long long>(nkp); d_state = cv.take<DState>(1); d_rank = cv.take<unsigned int>(sel_cap);
+            auto layout = [&](Carver &cv) {
+                d_img0 = cv.take<uint8_t>(area0); d_lvl = cv.take<uint8_t>(area0); d_aux = cv.take<uint8_t>(area0);
+                d_cand = cv.take<Cand>(area0 / 4 + 16); d_sel = cv.take<Cand>(sel_cap); d_pat = cv.take<int8_t>(32 * 1024);
+                d_kp = cv.take<int32_t>(nkp * 4); d_dir = cv.take<int32_t>(nkp); d_desc = cv.take<uint8_t>(nkp * 32);
+                d_count = cv.take<unsigned int>(1); d_dirs = cv.take<int32_t>(64); d_hist = cv.take<unsigned int>(2048);
+                d_xy = cv.take<float>(nkp * 2); d_resp = cv.take<long long>(nkp); d_state = cv.take<DState>(1); d_rank = cv.take<unsigned int>(sel_cap);
+            };
+            Carver measure, cv;
+            layout(measure);
+            HIP_TRY(ws_reserve(ws, measure.off));
+            cv.base = ws->blk;
+            layout(cv);
         }
         HIP_TRY(hipMemcpy2DAsync(d_img0, (size_t)cols, img, (size_t)stride, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_pat, pattern, 32 * 1024, hipMemcpyHostToDevice, st));
@@ -710,8 +706,8 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
         if (!verbose && getenv("SID_ORB_HOST_SELECT") == nullptr) {
             const DevBufs B{d_img0, d_lvl, d_aux, d_desc, d_cand, d_sel, d_pat, d_dirs, d_kp, d_hist, d_xy, d_resp, d_state, d_rank};
             bool overflow = false;
-            rc = detect_on_device(ws, B, rows, cols, P, sc, lr, lc, want, sel_cap, xy, meta, response, desc, max_out, &total, &overflow);
-            if (rc != SID_PM_OK || !overflow) { *n_out = rc == SID_PM_OK ? total : 0; goto done; }
+            const int rc = detect_on_device(ws, B, rows, cols, P, sc, lr, lc, want, sel_cap, xy, meta, response, desc, max_out, &total, &overflow);
+            if (rc != SID_PM_OK || !overflow) { *n_out = rc == SID_PM_OK ? total : 0; return rc; }
             total = 0;
         }
         for (int l = 0; l < L && total < max_out; ++l) {
@@ -734,7 +730,7 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
             HIP_TRY(hipStreamSynchronize(st));
             nc = ws->h_small[0];
             tick("resize + fast + nms", l);
-            if (nc > cap) { rc = fail(SID_PM_ERR_HIP, "candidate list overflow (cannot happen: one maximum per 2x2 block)"); goto done; }
+            if (nc > cap) return fail(SID_PM_ERR_HIP, "candidate list overflow (cannot happen: one maximum per 2x2 block)");
             if (nc == 0) continue;
             hipLaunchKernelGGL(k_harris, dim3((nc + 255) / 256), dim3(256), 0, st, lvl, c, d_cand, nc);
             const Cand *d_src = d_cand;
@@ -776,7 +772,7 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
             int64_t n = std::min<int64_t>(std::min<int64_t>(nc, want[l]), max_out - total);
             kp.resize((size_t)(4 * n));
             for (int64_t i = 0; i < n; ++i) { kp[4 * i] = cand[(size_t)i].x; kp[4 * i + 1] = cand[(size_t)i].y; kp[4 * i + 2] = l; kp[4 * i + 3] = 0; }
-            if ((size_t)n > nkp) { rc = fail(SID_PM_ERR_HIP, "level key points exceed the workspace (cannot happen)"); goto done; }
+            if ((size_t)n > nkp) return fail(SID_PM_ERR_HIP, "level key points exceed the workspace (cannot happen)");
             HIP_TRY(hipMemcpyAsync(d_kp, kp.data(), (size_t)(4 * n) * sizeof(int32_t), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_orient, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, lvl, c, d_kp, (int)n, R, d_dirs, d_dir);
             hipLaunchKernelGGL(k_blur, grd, blk, 0, st, lvl, r, c, d_aux);                // the score map is no longer needed
@@ -799,9 +795,5 @@ SID_EXPORT int sid_orb_detect(int device, const uint8_t *img, int64_t rows, int6
         }
         *n_out = total;
     }
-done:
-    if (st) (void)hipStreamSynchronize(st);                            // (nothing of this call may still be in flight in a workspace that is free)
-    ws_release(ws);
-    (void)hipSetDevice(prev);
-    return rc;
+    return SID_PM_OK;
 }

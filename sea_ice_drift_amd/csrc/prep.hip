@@ -10,27 +10,17 @@
 //   mean_kernel       the float64 polynomial image alone (get_spatial_mean)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 #include <algorithm>
 
 #include "../../include/sid_prep.h"
-#include "../../include/sid_pm.h"
+#include "host_util.h"
 #include "prep_pixel.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kUnroll = 2;               // 16-byte words in flight per lane and array
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 struct Coef { double c[6]; };            // x[0] of the reference's lstsq: col, col^2, row, row^2, col*row, 1
 
@@ -164,27 +154,6 @@ int check_plane(const void *p, int64_t cols, int64_t stride, const char *what)
 bool aligned(const void *p, int64_t stride, int64_t item, uintptr_t bytes)
 {
     return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0 && ((uintptr_t)(stride * item) & (bytes - 1)) == 0;
-}
-
-// launches go to the device that holds the image (the null stream belongs to the CURRENT device)
-struct DeviceOf {
-    int prev = -1;
-    explicit DeviceOf(const void *p)
-    {
-        hipPointerAttribute_t at;
-        int cur = 0; (void)hipGetDevice(&cur);
-        if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device != cur) {
-            prev = cur; (void)hipSetDevice(at.device);
-        } else (void)hipGetLastError();                      // (a pointer HIP does not know leaves an error behind)
-    }
-    ~DeviceOf() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-    return SID_PM_OK;
 }
 
 template <bool VEC>

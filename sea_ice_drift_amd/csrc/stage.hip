@@ -9,8 +9,6 @@
 // A workspace handle (sid_stage_create) owns the device and pinned host buffers: no allocation per call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <string.h>
 #include <stdlib.h>
 #include <math.h>
@@ -18,20 +16,11 @@
 #include <vector>
 
 #include "../../include/sid_stage.h"
-#include "../../include/sid_pm.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
 
 // monotone key: a < b  <=>  key(a) < key(b) for all non-NaN floats (-0.0 sorts before +0.0, which NumPy's
 // sort may order either way - they are equal as values, so every order statistic is the same value)

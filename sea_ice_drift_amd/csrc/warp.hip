@@ -10,18 +10,13 @@
 // pixel has one owner the order of the items does not reach the result.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
-#include <mutex>
 
 #include "../../include/sid_grid.h"
-#include "../../include/sid_pm.h"
 #include "../../include/sid_warp.h"
+#include "host_util.h"
 #include "warp_pixel.h"
-
-#define SID_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
 
@@ -34,13 +29,6 @@ static_assert(sid_warp::kTileRows == SID_WARP_TILE_ROWS && sid_warp::kTileCols =
 static_assert(sid_warp::kU8 == SID_WARP_U8 && sid_warp::kF32 == SID_WARP_F32 && sid_warp::kKeepZero == SID_WARP_KEEP_ZERO, "codes of sid_warp.h");
 static_assert(sid_grid::kShorter == SID_GRID_DIAG_SHORTER && sid_grid::kMain == SID_GRID_DIAG_MAIN && sid_grid::kAnti == SID_GRID_DIAG_ANTI,
               "diagonal codes of sid_grid.h");
-
-thread_local char g_err[256] = "";
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
-    return code;
-}
 
 constexpr int kBlock = 256, kWaves = kBlock / 64, kScanBlock = 1024, kScanPer = 4;
 static_assert(sid_warp::kTileCols == 64 && sid_warp::kTileRows % kWaves == 0, "one wavefront per tile row");
@@ -236,8 +224,6 @@ int check_args(const void *x, const void *y, const void *xs, const void *ys, int
 }
 
 // ---------------------------------------------------------------- launches
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(SID_PM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
 unsigned blocks_for(int64_t threads, int64_t cap)
 {
     const int64_t b = (threads + kBlock - 1) / kBlock;
@@ -246,28 +232,30 @@ unsigned blocks_for(int64_t threads, int64_t cap)
 
 int launch_fill(void *base, int64_t pitch, int64_t row_bytes, int64_t rows, uint32_t pat, int cus, hipStream_t st)
 {
-    int rc = SID_PM_OK;
-    if (!base || rows == 0 || row_bytes == 0) return rc;
+    if (!base || rows == 0 || row_bytes == 0) return SID_PM_OK;
     hipLaunchKernelGGL(k_warp_fill, dim3(blocks_for(rows * (row_bytes / 16 + 2), (int64_t)cus * 32)), dim3(kBlock), 0, st,
                        static_cast<unsigned char *>(base), pitch, row_bytes, rows, pat);
     HIP_TRY(hipGetLastError());
-done:
-    return rc;
+    return SID_PM_OK;
+}
+
+size_t cell_count(int64_t grid_rows, int64_t grid_cols)
+{
+    return grid_rows >= 2 && grid_cols >= 2 ? (size_t)((grid_rows - 1) * (grid_cols - 1)) : 0;
 }
 
 // All of one call; `off` holds (cells + 1) int64
 int launch_all(const Nodes &g, const Images &im, int dtype, double fill, int64_t *off, int cus, hipStream_t st)
 {
-    int rc = SID_PM_OK;
     const Fill f = fill_patterns(dtype, fill);
     const int64_t es = dtype == SID_WARP_U8 ? 1 : 4;
-    const int64_t cells = g.rows >= 2 && g.cols >= 2 ? (g.rows - 1) * (g.cols - 1) : 0;
-    if (im.rows_o == 0 || im.cols_o == 0) return rc;
-    if ((rc = launch_fill(im.out, im.out_stride * es, im.cols_o * es, im.rows_o, f.out, cus, st))) return rc;
-    if ((rc = launch_fill(im.covered, im.cols_o, im.cols_o, im.rows_o, 0u, cus, st))) return rc;
-    if ((rc = launch_fill(im.map_x, im.cols_o * 4, im.cols_o * 4, im.rows_o, f.nan, cus, st))) return rc;
-    if ((rc = launch_fill(im.map_y, im.cols_o * 4, im.cols_o * 4, im.rows_o, f.nan, cus, st))) return rc;
-    if (cells == 0) return rc;
+    const int64_t cells = (int64_t)cell_count(g.rows, g.cols);
+    if (im.rows_o == 0 || im.cols_o == 0) return SID_PM_OK;
+    if (int rc = launch_fill(im.out, im.out_stride * es, im.cols_o * es, im.rows_o, f.out, cus, st)) return rc;
+    if (int rc = launch_fill(im.covered, im.cols_o, im.cols_o, im.rows_o, 0u, cus, st)) return rc;
+    if (int rc = launch_fill(im.map_x, im.cols_o * 4, im.cols_o * 4, im.rows_o, f.nan, cus, st)) return rc;
+    if (int rc = launch_fill(im.map_y, im.cols_o * 4, im.cols_o * 4, im.rows_o, f.nan, cus, st)) return rc;
+    if (cells == 0) return SID_PM_OK;
     hipLaunchKernelGGL(k_warp_count, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g, im.rows_o, im.cols_o, cells, off);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_warp_scan, dim3(1), dim3(kScanBlock), 0, st, off, cells);
@@ -275,8 +263,7 @@ int launch_all(const Nodes &g, const Images &im, int dtype, double fill, int64_t
     if (dtype == SID_WARP_U8) hipLaunchKernelGGL(k_warp_walk<uint8_t>, dim3((unsigned)cus * 8), dim3(kBlock), 0, st, g, im, off, cells);
     else hipLaunchKernelGGL(k_warp_walk<float>, dim3((unsigned)cus * 8), dim3(kBlock), 0, st, g, im, off, cells);
     HIP_TRY(hipGetLastError());
-done:
-    return rc;
+    return SID_PM_OK;
 }
 
 void host_all(const Nodes &g, const Images &im, int dtype, double fill)
@@ -292,23 +279,15 @@ void host_all(const Nodes &g, const Images &im, int dtype, double fill)
     else host_walk<float>(g, im);
 }
 
-// Per device: the offsets of the device entry point, a staging block for the host-buffer entry point (both grow-only) and the
-// number of compute units.  Calls are serialised by the mutex.
-struct Dev { unsigned char *blk = nullptr; size_t cap = 0; int64_t *off = nullptr; size_t off_cap = 0; int cus = 0; };
-std::mutex g_mu;
-Dev g_dev[16];
-
-int grow(unsigned char *&p, size_t &cap, size_t bytes)
-{
-    if (cap >= bytes) return SID_PM_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SID_PM_ERR_NOMEM : SID_PM_ERR_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
-    cap = want;
-    return SID_PM_OK;
-}
+// Per device, beside the pool's staging block of the host-buffer entry point: the offsets of the device entry point (grow-only
+// too) and the number of compute units.  Calls are serialised by the pool's mutex.
+struct Offsets {
+    unsigned char *off = nullptr; size_t off_cap = 0; int cus = 0;
+    bool cached() const { return off != nullptr; }
+    void free() { if (off) (void)hipFree(off); }
+};
+using Dev = DevicePool<Offsets>::Slot;
+DevicePool<Offsets> g_pool;
 
 int compute_units(Dev &d, int device)
 {
@@ -320,40 +299,11 @@ int compute_units(Dev &d, int device)
     return SID_PM_OK;
 }
 
-int pick_device(int device, int &prev)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n || device >= 16) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
-    (void)hipGetDevice(&prev); (void)hipSetDevice(device);
-    return SID_PM_OK;
-}
-
-size_t up(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 SID_EXPORT const char *sid_warp_last_error(void) { return g_err; }
 
-SID_EXPORT int sid_warp_release(int device)
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    int prev = 0;
-    bool any = false;
-    for (int i = 0; i < 16; ++i) any = any || ((device < 0 || i == device) && (g_dev[i].blk || g_dev[i].off));
-    if (!any) return SID_PM_OK;
-    (void)hipGetDevice(&prev);
-    for (int i = 0; i < 16; ++i) {
-        if (device >= 0 && i != device) continue;
-        Dev &d = g_dev[i];
-        if (!d.blk && !d.off) continue;
-        (void)hipSetDevice(i);
-        if (d.blk) (void)hipFree(d.blk);
-        if (d.off) (void)hipFree(d.off);
-        d = Dev();
-    }
-    (void)hipSetDevice(prev);
-    return SID_PM_OK;
-}
+SID_EXPORT int sid_warp_release(int device) { return g_pool.release(device); }
 
 SID_EXPORT int sid_warp_image_device(const double *x, const double *y, const double *xs, const double *ys, const uint8_t *valid,
                                      int64_t grid_rows, int64_t grid_cols,
@@ -366,18 +316,14 @@ SID_EXPORT int sid_warp_image_device(const double *x, const double *y, const dou
         return rc;
     if (rows_o == 0 || cols_o == 0) return SID_PM_OK;
     int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 16) return fail(SID_PM_ERR_NODEVICE, "no current HIP device");
+    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= kMaxDevices) return fail(SID_PM_ERR_NODEVICE, "no current HIP device");
     const Nodes g = {x, y, xs, ys, valid, grid_rows, grid_cols, diagonal};
     const Images im = {src, rows_s, cols_s, src_stride, rows_o, cols_o, order, flags, out, out_stride, covered, map_x, map_y};
-    const size_t cells = grid_rows >= 2 && grid_cols >= 2 ? (size_t)((grid_rows - 1) * (grid_cols - 1)) : 0;
-    std::lock_guard<std::mutex> lock(g_mu);
-    Dev &d = g_dev[device];
+    std::lock_guard<std::mutex> lock(g_pool.mutex(device));
+    Dev &d = g_pool.slot[device];
     if (int rc = compute_units(d, device)) return rc;
-    unsigned char *p = reinterpret_cast<unsigned char *>(d.off);
-    const int rc = grow(p, d.off_cap, sizeof(int64_t) * (cells + 1));
-    d.off = reinterpret_cast<int64_t *>(p);
-    if (rc) return rc;
-    return launch_all(g, im, dtype, fill, d.off, d.cus, reinterpret_cast<hipStream_t>(hip_stream));
+    if (int rc = grow(d.off, d.off_cap, sizeof(int64_t) * (cell_count(grid_rows, grid_cols) + 1))) return rc;
+    return launch_all(g, im, dtype, fill, reinterpret_cast<int64_t *>(d.off), d.cus, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 SID_EXPORT int sid_warp_image(int device, const double *x, const double *y, const double *xs, const double *ys, const uint8_t *valid,
@@ -386,9 +332,9 @@ SID_EXPORT int sid_warp_image(int device, const double *x, const double *y, cons
                               int64_t rows_o, int64_t cols_o, int order, double fill, int diagonal, uint32_t flags,
                               void *out, int64_t out_stride, uint8_t *covered, float *map_x, float *map_y)
 {
-    if (int rc0 = check_args(x, y, xs, ys, grid_rows, grid_cols, src, dtype, rows_s, cols_s, src_stride, rows_o, cols_o, order, fill,
-                             diagonal, flags, out, out_stride, covered, map_x, map_y))
-        return rc0;
+    if (int rc = check_args(x, y, xs, ys, grid_rows, grid_cols, src, dtype, rows_s, cols_s, src_stride, rows_o, cols_o, order, fill,
+                            diagonal, flags, out, out_stride, covered, map_x, map_y))
+        return rc;
     if (rows_o == 0 || cols_o == 0) return SID_PM_OK;
     if (device == -1) {
         const Nodes g = {x, y, xs, ys, valid, grid_rows, grid_cols, diagonal};
@@ -396,50 +342,45 @@ SID_EXPORT int sid_warp_image(int device, const double *x, const double *y, cons
         host_all(g, im, dtype, fill);
         return SID_PM_OK;
     }
-    int prev = 0;
-    if (int rc0 = pick_device(device, prev)) return rc0;
-    int rc = SID_PM_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        Dev &d = g_dev[device];
-        const size_t es = dtype == SID_WARP_U8 ? 1 : 4;
-        const size_t n = (size_t)(grid_rows * grid_cols), nb = sizeof(double) * n;
-        const size_t cells = grid_rows >= 2 && grid_cols >= 2 ? (size_t)((grid_rows - 1) * (grid_cols - 1)) : 0;
-        const size_t npx = (size_t)rows_o * (size_t)cols_o, nsrc = src ? (size_t)rows_s * (size_t)cols_s : 0;
-        // offsets, x, y, xs, ys, valid, source, out, covered, map_x, map_y
-        const size_t o_nodes = up(sizeof(int64_t) * (cells + 1)), o_valid = o_nodes + 4 * up(nb), o_src = o_valid + up(n);
-        const size_t o_out = o_src + up(nsrc * es), o_cov = o_out + up(out ? npx * es : 0), o_mx = o_cov + up(covered ? npx : 0);
-        const size_t o_my = o_mx + up(map_x ? npx * 4 : 0), o_end = o_my + up(map_y ? npx * 4 : 0);
-        unsigned char *b;
-        if ((rc = compute_units(d, device))) goto done;
-        if ((rc = grow(d.blk, d.cap, o_end))) goto done;
-        b = d.blk;
-        {
-            const double *nodes[4] = {x, y, xs, ys};
-            for (int j = 0; j < 4 && n; ++j) HIP_TRY(hipMemcpyAsync(b + o_nodes + j * up(nb), nodes[j], nb, hipMemcpyHostToDevice, 0));
-        }
-        if (valid && n) HIP_TRY(hipMemcpyAsync(b + o_valid, valid, n, hipMemcpyHostToDevice, 0));
-        if (nsrc)
-            HIP_TRY(hipMemcpy2DAsync(b + o_src, (size_t)cols_s * es, src, (size_t)src_stride * es, (size_t)cols_s * es, (size_t)rows_s,
-                                     hipMemcpyHostToDevice, 0));
-        {
-            const double *dn = reinterpret_cast<const double *>(b + o_nodes);
-            const size_t o = up(nb) / sizeof(double);
-            const Nodes g = {dn, dn + o, dn + 2 * o, dn + 3 * o, valid ? b + o_valid : nullptr, grid_rows, grid_cols, diagonal};
-            const Images im = {src ? b + o_src : nullptr, rows_s, cols_s, cols_s, rows_o, cols_o, order, flags,
-                               out ? b + o_out : nullptr, cols_o, covered ? b + o_cov : nullptr,
-                               map_x ? reinterpret_cast<float *>(b + o_mx) : nullptr, map_y ? reinterpret_cast<float *>(b + o_my) : nullptr};
-            if ((rc = launch_all(g, im, dtype, fill, reinterpret_cast<int64_t *>(b), d.cus, 0))) goto done;
-        }
-        if (out)
-            HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * es, b + o_out, (size_t)cols_o * es, (size_t)cols_o * es, (size_t)rows_o,
-                                     hipMemcpyDeviceToHost, 0));
-        if (covered) HIP_TRY(hipMemcpyAsync(covered, b + o_cov, npx, hipMemcpyDeviceToHost, 0));
-        if (map_x) HIP_TRY(hipMemcpyAsync(map_x, b + o_mx, npx * 4, hipMemcpyDeviceToHost, 0));
-        if (map_y) HIP_TRY(hipMemcpyAsync(map_y, b + o_my, npx * 4, hipMemcpyDeviceToHost, 0));
-        HIP_TRY(hipStreamSynchronize(0));
-    }
-done:
-    (void)hipSetDevice(prev);
-    return rc;
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    Dev &d = g_pool.slot[device];
+    const size_t es = dtype == SID_WARP_U8 ? 1 : 4;
+    const size_t n = (size_t)(grid_rows * grid_cols), nb = sizeof(double) * n;
+    const size_t npx = (size_t)rows_o * (size_t)cols_o, nsrc = src ? (size_t)rows_s * (size_t)cols_s : 0;
+    int64_t *d_off;
+    double *d_nodes[4];
+    uint8_t *d_valid, *d_cov;
+    unsigned char *d_src, *d_out;
+    float *d_mx, *d_my;
+    if (int rc = compute_units(d, device)) return rc;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            d_off = c.take<int64_t>(cell_count(grid_rows, grid_cols) + 1);
+            for (double *&q : d_nodes) q = c.take<double>(n);
+            d_valid = c.take<uint8_t>(n, valid != nullptr);
+            d_src = c.take<unsigned char>(nsrc * es);
+            d_out = c.take<unsigned char>(npx * es, out != nullptr);
+            d_cov = c.take<uint8_t>(npx, covered != nullptr);
+            d_mx = c.take<float>(npx, map_x != nullptr);
+            d_my = c.take<float>(npx, map_y != nullptr);
+        }))
+        return rc;
+    const double *nodes[4] = {x, y, xs, ys};
+    for (int j = 0; j < 4 && n; ++j) HIP_TRY(hipMemcpyAsync(d_nodes[j], nodes[j], nb, hipMemcpyHostToDevice, 0));
+    if (d_valid) HIP_TRY(hipMemcpyAsync(d_valid, valid, n, hipMemcpyHostToDevice, 0));
+    if (d_src)
+        HIP_TRY(hipMemcpy2DAsync(d_src, (size_t)cols_s * es, src, (size_t)src_stride * es, (size_t)cols_s * es, (size_t)rows_s,
+                                 hipMemcpyHostToDevice, 0));
+    const Nodes g = {d_nodes[0], d_nodes[1], d_nodes[2], d_nodes[3], d_valid, grid_rows, grid_cols, diagonal};
+    const Images im = {d_src, rows_s, cols_s, cols_s, rows_o, cols_o, order, flags, d_out, cols_o, d_cov, d_mx, d_my};
+    if (int rc = launch_all(g, im, dtype, fill, d_off, d.cus, 0)) return rc;
+    if (out)
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * es, d_out, (size_t)cols_o * es, (size_t)cols_o * es, (size_t)rows_o,
+                                 hipMemcpyDeviceToHost, 0));
+    if (covered) HIP_TRY(hipMemcpyAsync(covered, d_cov, npx, hipMemcpyDeviceToHost, 0));
+    if (map_x) HIP_TRY(hipMemcpyAsync(map_x, d_mx, npx * 4, hipMemcpyDeviceToHost, 0));
+    if (map_y) HIP_TRY(hipMemcpyAsync(map_y, d_my, npx * 4, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
 }
