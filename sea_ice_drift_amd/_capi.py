@@ -64,6 +64,10 @@ PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean',
 # every symbol include/sid_mask.h declares (the invalid-pixel mask: zoomed water mask OR non-finite pixels; same library)
 MASK_SYMBOLS = ('sid_mask_workspace_bytes', 'sid_mask_landmask', 'sid_mask_invalid', 'sid_mask_last_error')
 
+# every symbol include/sid_resize.h declares (downsampling by area average, alone and as the front of the preparation; same library)
+RESIZE_SYMBOLS = ('sid_resize_f32', 'sid_resize_u8', 'sid_resize_prep_apply', 'sid_resize_prep_subsample', 'sid_resize_last_error')
+RESIZE_MAX_DIM = 1 << 24                                  # SID_RESIZE_MAX_DIM
+
 _u8p = C.POINTER(C.c_uint8)
 _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
@@ -209,6 +213,13 @@ def lib():
         L.sid_mask_landmask.argtypes = raster + plane + plane + [vp]
         L.sid_mask_invalid.argtypes = raster + plane + [C.c_int] + plane + [C.c_float] + plane + plane + [vp]
         L.sid_mask_last_error.restype = C.c_char_p
+    if hasattr(L, 'sid_resize_f32'):
+        vp, plane, i64 = C.c_void_p, [C.c_void_p, C.c_int64], C.c_int64
+        L.sid_resize_f32.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, vp]
+        L.sid_resize_u8.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, vp]
+        L.sid_resize_prep_apply.argtypes = [vp, i64, i64, i64] + plane + plane + [C.c_int, C.c_float, _f64p, vp, i64, i64, i64, vp]
+        L.sid_resize_prep_subsample.argtypes = [vp, i64, i64, i64] + plane + plane + [C.c_int, C.c_float, i64, i64, i64, vp, vp]
+        L.sid_resize_last_error.restype = C.c_char_p
     # SID_PM_LIB (A/B runs against the library of an earlier round) may lack the entry points added since
     optional = ('sid_pm_check', 'sid_pm_unpermute', 'sid_pm_rotate_and_match', 'sid_pm_get_template', 'sid_pm_get_hessian', 'sid_pm_estimate_run_time') if os.environ.get('SID_PM_LIB') else ()
     for name in SYMBOLS:
@@ -637,7 +648,7 @@ def _checker(unit, index_error=None):
 
 _ft_check, _stage_check, _fg_check = _checker('sid_ft'), _checker('sid_stage'), _checker('sid_fg')
 _defor_check, _grid_check, _warp_check = _checker('sid_defor', DEFOR_ERR_INDEX), _checker('sid_grid'), _checker('sid_warp')
-_prep_check, _mask_check = _checker('sid_prep'), _checker('sid_mask')
+_prep_check, _mask_check, _resize_check = _checker('sid_prep'), _checker('sid_mask'), _checker('sid_resize')
 
 
 def _vp(p):
@@ -970,3 +981,31 @@ def mask_invalid(wm, h, w, H, W, work_ptr, img, dB, ia, hh_factor, mask, wmz=Non
     _mask_check(lib().sid_mask_invalid(_vp(w_ptr), int(h), int(w), int(w_stride), int(H), int(W), _vp(work_ptr), _vp(img[0]), int(img[1]),
                                        int(bool(dB)), _vp(ia_ptr), int(ia_stride), float(hh_factor), _vp(mask[0]), int(mask[1]),
                                        _vp(z_ptr), int(z_stride), _vp(stream)))
+
+
+def resize(src, dtype, rows, cols, stride, dst, out_rows, out_cols, dst_stride, option, stream=0):
+    """``sid_resize_f32`` (``dtype`` 'float32'; ``option``: nan_omit) or ``sid_resize_u8`` ('uint8'; ``option``: zero_invalid) on raw
+    device pointers."""
+    fn = {'float32': lib().sid_resize_f32, 'uint8': lib().sid_resize_u8}[dtype]
+    _resize_check(fn(_vp(src), int(rows), int(cols), int(stride), _vp(dst), int(out_rows), int(out_cols), int(dst_stride),
+                     int(bool(option)), _vp(stream)))
+
+
+def resize_prep_apply(img, rows, cols, stride, ia, mask, dB, hh_factor, coeffs, out_ptr, out_rows, out_cols, out_stride, stream=0):
+    """``sid_resize_prep_apply`` on raw device pointers: ``prep_apply`` of the image and incidence angle averaged down to
+    ``out_rows`` x ``out_cols``; ``mask`` (pointer, row stride) has that shape."""
+    ia_ptr, ia_stride = ia if ia is not None else (0, 0)
+    m_ptr, m_stride = mask if mask is not None else (0, 0)
+    keep, cp = _prep_coeffs(coeffs)
+    _resize_check(lib().sid_resize_prep_apply(_vp(img), int(rows), int(cols), int(stride), _vp(ia_ptr), int(ia_stride),
+                                              _vp(m_ptr), int(m_stride), int(bool(dB)), float(hh_factor), cp,
+                                              _vp(out_ptr), int(out_rows), int(out_cols), int(out_stride), _vp(stream)))
+
+
+def resize_prep_subsample(img, rows, cols, stride, ia, mask, dB, hh_factor, step, out_rows, out_cols, sub_ptr, stream=0):
+    """``sid_resize_prep_subsample`` on raw device pointers: ``prep_subsample`` of the same reduced images."""
+    ia_ptr, ia_stride = ia if ia is not None else (0, 0)
+    m_ptr, m_stride = mask if mask is not None else (0, 0)
+    _resize_check(lib().sid_resize_prep_subsample(_vp(img), int(rows), int(cols), int(stride), _vp(ia_ptr), int(ia_stride),
+                                                  _vp(m_ptr), int(m_stride), int(bool(dB)), float(hh_factor), int(step),
+                                                  int(out_rows), int(out_cols), _vp(sub_ptr), _vp(stream)))

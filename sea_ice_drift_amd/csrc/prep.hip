@@ -22,22 +22,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kUnroll = 2;               // 16-byte words in flight per lane and array
 
-struct Coef { double c[6]; };            // x[0] of the reference's lstsq: col, col^2, row, row^2, col*row, 1
-
-// the polynomial at (row, col) in the reference's order of operations (lib.py:248-253); c2r = c[2] * row and
-// c3r2 = c[3] * row^2 are the same for a whole row
-__device__ __forceinline__ double spatial_mean(const Coef &K, int64_t col, double dr, double c2r, double c3r2)
-{
-    const double dc = (double)col, dc2 = (double)(col * col);
-    double m = K.c[0] * dc;
-    m = m + K.c[1] * dc2;
-    m = m + c2r;
-    m = m + c3r2;
-    m = m + (K.c[4] * dc) * dr;
-    m = m + K.c[5];
-    return m;
-}
-
 template <bool DB, bool HH, bool MASK, bool MEAN, bool VEC>
 __global__ __launch_bounds__(kThreads) void apply_kernel(const float *img, int64_t rows, int64_t cols, int64_t stride,
                                                          const float *ia, int64_t ia_stride, const uint8_t *mask, int64_t mask_stride,

@@ -1,5 +1,6 @@
 // prep_pixel.h - the per-pixel function of the sigma0 preparation (include/sid_prep.h: dB, HH correction, mask, detrend),
-// shared by prep.hip (which writes the pixel) and landmask.hip (which asks whether it is finite): one text, one result.
+// shared by prep.hip (which writes the pixel), landmask.hip (which asks whether it is finite) and resize.hip (which averages the
+// full-resolution planes first): one text, one result.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +51,22 @@ __device__ __forceinline__ float prep_pixel(bool db, bool hh, bool msk, bool mea
     if (msk) v = m ? nan : v;
     if (mean) v = (float)((double)v - mu);
     return v;
+}
+
+struct Coef { double c[6]; };            // x[0] of the reference's lstsq: col, col^2, row, row^2, col*row, 1
+
+// the polynomial at (row, col) in the reference's order of operations (lib.py:248-253); c2r = c[2] * row and
+// c3r2 = c[3] * row^2 are the same for a whole row
+__device__ __forceinline__ double spatial_mean(const Coef &K, int64_t col, double dr, double c2r, double c3r2)
+{
+    const double dc = (double)col, dc2 = (double)(col * col);
+    double m = K.c[0] * dc;
+    m = m + K.c[1] * dc2;
+    m = m + c2r;
+    m = m + c3r2;
+    m = m + (K.c[4] * dc) * dr;
+    m = m + K.c[5];
+    return m;
 }
 
 }  // namespace

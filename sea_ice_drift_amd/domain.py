@@ -63,6 +63,17 @@ class ArrayNansat(object):
             return lon * self.dst_scale, lat * self.dst_scale
         return lon, lat
 
+    def resized(self, factor=0.5, device=0):
+        """A new ArrayNansat with the image downsampled by area average on the GPU (``lib.resize_image`` with
+        ``zero_invalid=True``: a reduced pixel is 0, invalid, when one of its source pixels is) and the georeference carried
+        along: ``origin`` and ``dst_scale`` kept, ``matrix @ diag(cols / out_cols, rows / out_rows)``.  Pixel coordinates are
+        corner-based (``get_corners``), so the reduced object has the corners of this one.  This object is left unchanged."""
+        from . import lib
+        image = lib.resize_image(self.image, factor, zero_invalid=True, device=device)
+        rows, cols = self.image.shape
+        scale = np.diag([cols / image.shape[1], rows / image.shape[0]])
+        return ArrayNansat(image, origin=self.origin.copy(), matrix=self.matrix @ scale, dst_scale=self.dst_scale)
+
     def get_corners(self):
         rows, cols = self.image.shape
         c = np.array([0.0, 0.0, cols, cols])

@@ -3,7 +3,8 @@
 What ``pattern_matching`` touches: the two first-guess interpolators (reference lib.py:139-177 and
 :179-201), the grid scatter (lib.py:408-412) and a stand-in for ``nansat.NSR``; plus the uint8 staging step
 ``get_uint8_image`` (lib.py:27-59), whose two full-image passes run on the GPU (include/sid_stage.h), and the array steps of ``get_n`` in
-front of it (lib.py:318-331: dB, ``hh_angular_correction``, mask, ``get_spatial_mean``; include/sid_prep.h): ``prepare_image``.
+front of it (lib.py:318-331: dB, ``hh_angular_correction``, mask, ``get_spatial_mean``; include/sid_prep.h): ``prepare_image``,
+and the resize at its head (lib.py:314-316, ``n.resize(factor, resample_alg=-1)``; include/sid_resize.h): ``resize_image``.
 Reading files (lib.py:309-316, 333-340) and the geo/Haversine helpers are outside the hot path.
 """
 import numpy as np
@@ -389,6 +390,100 @@ def get_uint8_image(image, vmin, vmax, pmin, pmax, device=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# downsampling by area average: the first line of get_n, n.resize(factor, resample_alg=-1) (reference lib.py:314-316), on the
+# GPU (include/sid_resize.h)
+# ---------------------------------------------------------------------------------------------------------------------
+RESIZE_MAX_DIM = 1 << 24           # SID_RESIZE_MAX_DIM
+
+
+def resize_shape(rows, cols, factor=0.5, out_shape=None):
+    """The shape ``resize_image`` gives a ``rows`` x ``cols`` image: ``out_shape`` when given, else ``(int(rows * factor),
+    int(cols * factor))`` in Python float arithmetic (what nansat's ``resize(factor)`` is understood to do).  ValueError for a
+    factor that is not finite, not positive or above 1, for a dimension of 0 and for an ``out_shape`` beyond the image."""
+    import math
+    if out_shape is not None:
+        try:
+            r, c = (int(v) for v in out_shape)
+        except (TypeError, ValueError):
+            raise ValueError('out_shape: (rows, cols) expected, got %r' % (out_shape,))
+    else:
+        factor = float(factor)
+        if not math.isfinite(factor) or factor <= 0.0:
+            raise ValueError('factor: a finite positive number expected (got %r)' % (factor,))
+        if factor > 1.0:
+            raise ValueError('factor %r is above 1: downsampling only' % (factor,))
+        r, c = int(rows * factor), int(cols * factor)
+    if r < 1 or c < 1:
+        raise ValueError('a %d x %d image resized to %d x %d: an output dimension of 0' % (rows, cols, r, c))
+    if r > rows or c > cols:
+        raise ValueError('a %d x %d image resized to %d x %d: downsampling only' % (rows, cols, r, c))
+    if rows > RESIZE_MAX_DIM or cols > RESIZE_MAX_DIM:
+        raise ValueError('a %d x %d image: dimensions up to 2^24 are supported' % (rows, cols))
+    return r, c
+
+
+def _resize_kind(image):
+    """(is_tensor, dtype name, rows, cols) of a 2-D float32 or uint8 image: NumPy array or ROCm tensor with unit inner stride."""
+    import torch
+    is_tensor = isinstance(image, torch.Tensor)
+    if not is_tensor:
+        image = np.asarray(image)
+    name = str(image.dtype).replace('torch.', '')
+    if name not in ('float32', 'uint8'):
+        raise NotImplementedError('resize_image takes float32 and uint8 images (got %s)' % name)
+    if len(image.shape) != 2:
+        raise ValueError('image: 2-D array expected (got %d-D)' % len(image.shape))
+    if is_tensor:
+        if not image.is_cuda:
+            raise ValueError('a torch input must live on the GPU (pass NumPy arrays for host data)')
+        if image.stride(1) != 1 and image.shape[1] > 1:
+            raise NotImplementedError('image: unit inner stride expected (row stride is free)')
+    return is_tensor, name, int(image.shape[0]), int(image.shape[1])
+
+
+def _resize_device(t, name, out_rows, out_cols, option):
+    """``sid_resize_f32`` / ``sid_resize_u8`` of a device tensor on the current stream -> a new device tensor."""
+    import torch
+    from . import _capi
+    out = torch.empty((out_rows, out_cols), dtype=t.dtype, device=t.device)
+    _capi.resize(t.data_ptr(), name, int(t.shape[0]), int(t.shape[1]), int(t.stride(0)), out.data_ptr(), out_rows, out_cols,
+                 int(out.stride(0)), option, torch.cuda.current_stream(t.device).cuda_stream)
+    return out
+
+
+def resize_image(image, factor=0.5, out_shape=None, nan_policy='propagate', zero_invalid=True, device=0):
+    """Downsample a 2-D image by area average on the GPU: what ``n.resize(factor, resample_alg=-1)`` does to the band at the
+    head of the reference's ``get_n`` (lib.py:314-316), for a caller who holds the band as an array.  The result has
+    ``resize_shape(rows, cols, factor, out_shape)``; where rows and columns divide evenly (``factor=0.5`` on even sizes) every
+    output pixel is the mean of its k x k block, otherwise the exact area-weighted mean (include/sid_resize.h has the
+    weights and every rounding).  The same shape (``factor=1``) returns a copy with identical bits.
+
+    float32: float64 accumulation in row-major order, rounded once to float32; NaN and +-inf propagate, or
+    ``nan_policy='omit'`` leaves NaN pixels out of the sum and the divisor (a window of NaN alone gives NaN).  uint8: the mean
+    rounded half up in integer arithmetic; with ``zero_invalid`` (default: 0 means invalid throughout this package) an output
+    pixel is 0 exactly when one of its source pixels is.  An option of the other dtype given a non-default value raises
+    ValueError; other dtypes raise NotImplementedError.
+
+    A NumPy array is uploaded and a NumPy array comes back; a ROCm torch tensor (unit inner stride, any row stride) is read in
+    place on the current stream and a device tensor comes back.  The input is never modified.  No CPU fallback."""
+    import torch
+    is_tensor, name, rows, cols = _resize_kind(image)
+    if nan_policy not in ('propagate', 'omit'):
+        raise ValueError("nan_policy: 'propagate' or 'omit' expected (got %r)" % (nan_policy,))
+    if name == 'uint8' and nan_policy != 'propagate':
+        raise ValueError('nan_policy applies to float32 images (the image is uint8)')
+    if name == 'float32' and not zero_invalid:
+        raise ValueError('zero_invalid applies to uint8 images (the image is float32)')
+    out_rows, out_cols = resize_shape(rows, cols, factor, out_shape)
+    if (out_rows, out_cols) == (rows, cols):
+        return image.clone(memory_format=torch.contiguous_format) if is_tensor else np.array(image, copy=True, order='C')
+    option = (nan_policy == 'omit') if name == 'float32' else bool(zero_invalid)
+    t = image if is_tensor else _prep_upload(image, torch.device('cuda', device))
+    out = _resize_device(t, name, out_rows, out_cols, option)
+    return out if is_tensor else out.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # sigma0 preparation: the array half of get_n (reference lib.py:318-331) on the GPU (include/sid_prep.h)
 # ---------------------------------------------------------------------------------------------------------------------
 SPATIAL_MEAN_STEP = 50             # the reference's subsampling step of get_spatial_mean (lib.py:239)
@@ -472,11 +567,13 @@ def fit_spatial_mean(imgsub, step=SPATIAL_MEAN_STEP):
     return np.linalg.lstsq(predictors, z, rcond=None)[0]
 
 
-def _prep_subsample(t, ia, mask, dB, factor, stream):
-    """``[::50, ::50]`` of the image after dB / HH correction / mask, as a NumPy array (a few ten thousand samples)."""
+def _prep_subsample(t, ia, mask, dB, factor, stream, out_shape=None):
+    """``[::50, ::50]`` of the image after dB / HH correction / mask, as a NumPy array (a few ten thousand samples).
+    ``out_shape``: of the image and incidence angle averaged down to that shape first (``mask`` has that shape)."""
     import torch
     from . import _capi
-    rows, cols = int(t.shape[0]), int(t.shape[1])
+    full = (int(t.shape[0]), int(t.shape[1]))
+    rows, cols = full if out_shape is None else out_shape
     nrs, ncs = -(-rows // SPATIAL_MEAN_STEP), -(-cols // SPATIAL_MEAN_STEP)
     n = nrs * ncs
     dev_index = t.device.index or 0
@@ -486,23 +583,38 @@ def _prep_subsample(t, ia, mask, dB, factor, stream):
         ws = _PREP_WS[dev_index] = (torch.empty(cap, dtype=torch.float32, device=t.device),
                                     torch.empty(cap, dtype=torch.float32, pin_memory=True))
     d_sub, h_sub = ws
-    _capi.prep_subsample(t.data_ptr(), rows, cols, int(t.stride(0)), None if ia is None else _plane(ia),
-                         None if mask is None else _plane(mask), dB, factor, SPATIAL_MEAN_STEP, d_sub.data_ptr(), stream.cuda_stream)
+    if out_shape is None:
+        _capi.prep_subsample(t.data_ptr(), rows, cols, int(t.stride(0)), None if ia is None else _plane(ia),
+                             None if mask is None else _plane(mask), dB, factor, SPATIAL_MEAN_STEP, d_sub.data_ptr(), stream.cuda_stream)
+    else:
+        _capi.resize_prep_subsample(t.data_ptr(), full[0], full[1], int(t.stride(0)), None if ia is None else _plane(ia),
+                                    None if mask is None else _plane(mask), dB, factor, SPATIAL_MEAN_STEP, rows, cols,
+                                    d_sub.data_ptr(), stream.cuda_stream)
     with torch.cuda.stream(stream):
         h_sub[:n].copy_(d_sub[:n], non_blocking=True)
     stream.synchronize()
     return h_sub[:n].numpy().reshape(nrs, ncs).copy()
 
 
-def _prep_apply(image, incidence_angle, mask, dB, factor, remove_spatial_mean, coeffs, device):
-    """Checks, uploads and the one streaming pass: -> (float32 working image on the device, is_tensor)."""
+def _prep_apply(image, incidence_angle, mask, dB, factor, remove_spatial_mean, coeffs, device, resize=1):
+    """Checks, uploads and the one streaming pass: -> (float32 working image on the device, is_tensor).  ``resize`` != 1: the
+    pass averages ``image`` and ``incidence_angle`` down to ``resize_shape(rows, cols, resize)`` first (include/sid_resize.h);
+    ``mask`` has that shape."""
     import torch
     from . import _capi
     is_tensor, rows, cols = _prep_kind(image)
+    out_shape = None
+    if resize != 1:
+        out_shape = resize_shape(rows, cols, resize)
+        if out_shape == (rows, cols):
+            out_shape = None
     if incidence_angle is not None:
         incidence_angle = _prep_side(incidence_angle, 'incidence_angle', is_tensor, (rows, cols))
     if mask is not None:
-        mask = _prep_side(mask, 'mask', is_tensor, (rows, cols), mask=True)
+        if out_shape is not None and tuple(np.shape(mask)) != out_shape:
+            raise ValueError('mask: shape %s differs from %s, the shape of the %s image at factor=%r (the mask refers to the '
+                             'reduced image)' % (tuple(np.shape(mask)), out_shape, (rows, cols), resize))
+        mask = _prep_side(mask, 'mask', is_tensor, out_shape or (rows, cols), mask=True)
     if coeffs is not None:
         coeffs = _prep_coeffs(coeffs)
     if rows < 1 or cols < 1:
@@ -513,8 +625,13 @@ def _prep_apply(image, incidence_angle, mask, dB, factor, remove_spatial_mean, c
     mk = None if mask is None else (mask if is_tensor else _prep_upload(mask, dev, mask=True))
     stream = torch.cuda.current_stream(dev)
     if remove_spatial_mean and coeffs is None:
-        coeffs = fit_spatial_mean(_prep_subsample(t, ia, mk, dB, factor, stream))
-    work = torch.empty((rows, cols), dtype=torch.float32, device=dev)
+        coeffs = fit_spatial_mean(_prep_subsample(t, ia, mk, dB, factor, stream, out_shape))
+    work = torch.empty(out_shape or (rows, cols), dtype=torch.float32, device=dev)
+    if out_shape is not None:
+        _capi.resize_prep_apply(t.data_ptr(), rows, cols, int(t.stride(0)), None if ia is None else _plane(ia),
+                                None if mk is None else _plane(mk), dB, factor, coeffs if remove_spatial_mean else None,
+                                work.data_ptr(), out_shape[0], out_shape[1], int(work.stride(0)), stream.cuda_stream)
+        return work, is_tensor
     _capi.prep_apply(t.data_ptr(), rows, cols, int(t.stride(0)), None if ia is None else _plane(ia),
                      None if mk is None else _plane(mk), dB, factor, coeffs if remove_spatial_mean else None,
                      work.data_ptr(), int(work.stride(0)), stream.cuda_stream)
@@ -704,7 +821,8 @@ def prepare_image(image, dB=True, incidence_angle=None, correct_hh_factor=-0.27,
     the float64 ``log10`` rounded once, which NumPy's own float32 ``log10`` misses by 1 ulp on about half of all inputs
     (DESIGN.md section 16 has what that means for the uint8 image).  No CPU fallback.
 
-    ``prepare_image_masked`` below is this function with ``get_n``'s ``mask_invalid`` step computed on the device as well."""
+    ``prepare_image_masked`` below is this function with ``get_n``'s ``mask_invalid`` step computed on the device as well,
+    ``prepare_image_resized`` is both with ``get_n``'s resize in front."""
     work, is_tensor = _prep_apply(image, incidence_angle, mask, bool(dB), float(correct_hh_factor), bool(remove_spatial_mean),
                                   spatial_mean_coeffs, device)
     out = get_uint8_image(work, vmin, vmax, pmin, pmax)
@@ -720,15 +838,40 @@ def prepare_image_masked(image, dB=True, incidence_angle=None, correct_hh_factor
     at 1 / landmask_border of the resolution, of the image's kind - land: ``invalid_mask``), ORs ``mask`` in when one is given,
     and that plane is the mask of ``prepare_image``'s steps; it never leaves the device.  So +-inf become NaN before the
     percentiles, as in ``get_n``.  ``watermask`` without ``mask_invalid=True`` raises ValueError."""
+    return prepare_image_resized(image, 1, dB, incidence_angle, correct_hh_factor, mask, remove_spatial_mean, vmin, vmax, pmin, pmax,
+                                 device, spatial_mean_coeffs, mask_invalid, watermask)
+
+
+def prepare_image_resized(image, factor=0.5, dB=True, incidence_angle=None, correct_hh_factor=-0.27, mask=None,
+                          remove_spatial_mean=False, vmin=None, vmax=None, pmin=10, pmax=99, device=0, spatial_mean_coeffs=None,
+                          mask_invalid=False, watermask=None):
+    """``prepare_image_masked`` with ``get_n``'s resize in front (``factor``, ``get_n``'s own first keyword with its default;
+    the two functions above keep the signatures their callers know): ``image`` and ``incidence_angle`` are full resolution
+    and are averaged down as ``resize_image(..., factor)`` does, in the same pass as dB, HH correction, mask and detrend - the
+    reduced float images are never written; the result equals ``prepare_image(resize_image(image, factor),
+    incidence_angle=resize_image(incidence_angle, factor), ...)`` bit for bit.  ``mask``, and the shape ``watermask`` is
+    zoomed to, refer to the reduced image, as in ``get_n``, where the mask is computed after the resize: a mask of another
+    shape raises ValueError naming both.  The detrend is fitted to every 50th pixel of the reduced image.  With
+    ``mask_invalid=True`` the two planes are averaged down by ``resize_image`` first (the invalid-pixel mask reads the
+    reduced image a second time, so it is written once) and the rest is ``prepare_image_masked``'s route.  ``factor=1``:
+    no resize."""
     if watermask is not None and not mask_invalid:
         raise ValueError('watermask: needs mask_invalid=True')
     if not mask_invalid:
-        return prepare_image(image, dB, incidence_angle, correct_hh_factor, mask, remove_spatial_mean, vmin, vmax, pmin, pmax, device,
-                             spatial_mean_coeffs)
+        work, is_tensor = _prep_apply(image, incidence_angle, mask, bool(dB), float(correct_hh_factor), bool(remove_spatial_mean),
+                                      spatial_mean_coeffs, device, factor)
+        out = get_uint8_image(work, vmin, vmax, pmin, pmax)
+        return out if is_tensor else out.cpu().numpy()
     import torch
     is_tensor, rows, cols = _prep_kind(image)
     if incidence_angle is not None:
         incidence_angle = _prep_side(incidence_angle, 'incidence_angle', is_tensor, (rows, cols))
+    if factor != 1:
+        full = (rows, cols)
+        rows, cols = resize_shape(rows, cols, factor)
+        if mask is not None and tuple(np.shape(mask)) != (rows, cols):
+            raise ValueError('mask: shape %s differs from %s, the shape of the %s image at factor=%r (the mask refers to the '
+                             'reduced image)' % (tuple(np.shape(mask)), (rows, cols), full, factor))
     if mask is not None:
         mask = _prep_side(mask, 'mask', is_tensor, (rows, cols), mask=True)
     if spatial_mean_coeffs is not None:
@@ -742,6 +885,10 @@ def prepare_image_masked(image, dB=True, incidence_angle=None, correct_hh_factor
     up = (lambda a, **k: a) if is_tensor else (lambda a, **k: _prep_upload(a, dev, **k))
     image = up(image)
     incidence_angle = None if incidence_angle is None else up(incidence_angle)
+    if (rows, cols) != (int(image.shape[0]), int(image.shape[1])):
+        with torch.cuda.device(dev):
+            image = _resize_device(image, 'float32', rows, cols, False)
+            incidence_angle = None if incidence_angle is None else _resize_device(incidence_angle, 'float32', rows, cols, False)
     plane = _invalid_plane(image, incidence_angle, bool(dB), float(correct_hh_factor), None if watermask is None else up(watermask))
     if mask is not None:
         plane |= (up(mask, mask=True) != 0).view(torch.uint8)
