@@ -12,15 +12,16 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
 #include "../../include/sid_pm.h"
 #include "pm_kernel.h"
 #include "pm_large.h"
+#include "pm_plan.h"
+
+using namespace sid::plan;   // the launch planner: Switches, Plan, Bucket and the decision functions
 
 static_assert(SID_PM_SUBPIXEL == sid::kSubpixel, "the kernels test the bit of include/sid_pm.h");
 
@@ -54,8 +55,6 @@ struct Image {
     const uint8_t *ptr = nullptr;       // device
     int64_t rows = 0, cols = 0, stride = 0;
 };
-
-struct Bucket { int offset, count, lds, band, pitch, occ; uint32_t gs_stride = 0; bool big = false; bool keep = false; bool pooled = false; };   // pooled: the launch takes its blocks of global memory from the free lists (PMArgs::ring)   // keep: the launch keeps the sweep's accumulators (PMArgs::gs_keep_acc) and takes recycled blocks   // gs_stride: largest sum w'^2 block of the launch's points, in u32 entries (gs launches; 0 otherwise)   // occ: wavefronts per SIMD of the kernel build (3; 4: the four-per-CU class of the slot-group layouts); band: output rows per sweep work item of this launch (4 or 8); pitch: compile-time window pitch of the row-pair kernel (0: run-time)
 
 template <typename T>
 struct DevBuf {
@@ -99,11 +98,9 @@ struct sid_pm_ctx {
     int32_t *d_order = nullptr;
     double *d_angles = nullptr, *d_rot = nullptr;
     uint16_t *d_samp = nullptr;         // sampling table of the kernel (make_samp)
-    uint32_t *d_samp2 = nullptr;        // ... sorted per angle for the row-pair kernel (make_samp2; SID_PM_NO_SAMP2=1: not built)
+    uint32_t *d_samp2 = nullptr;        // ... sorted per angle for the row-pair kernel (make_samp2; SID_PM_SAMP2=1: built)
     bool rp = false;                    // the resident points run the row-pair kernel (decided at set_points: use_rp) ...
     int rp_paired = 0;                  // ... with slot groups: 0 none, 1 two groups (<= 7 angles), 2 four groups (<= 3 angles)
-    bool gs_keep_si = true;             // the blocks of global memory are sized for sum w' as well (classify_points; SID_PM_NO_GSI=1: not)
-    bool gs_keep_acc = false;           // ... or for the sweep's accumulators (PMArgs::gs_keep_acc; classify_points: keep_acc_policy)
     bool have_samp = false;             // SID_PM_NO_SAMP_TABLE=1 keeps the on-the-fly sampling (tests of the general sampler)
     int samp_nflag = 0;
     // host copies of what the classification needs: the launch classes depend on the shape of image 2, so a
@@ -117,16 +114,13 @@ struct sid_pm_ctx {
     DevBuf<uint32_t> d_goff;            // ... and the offset of every launch position's block in it (units of 64 entries)
     DevBuf<sid::PointRec> d_rec;        // row-pair kernel: one record per launch position (index, block offset, the five inputs)
     DevBuf<uint32_t> ring, pool;        // recycled blocks of the launches that keep accumulators (PMArgs::ring / pool; SID_PM_NO_RECYCLE=1: none)
-    uint32_t pool_stride = 0;           // u32 entries per recycled block: the largest block of any launch that takes them
     int32_t *h_refused = nullptr;       // pinned, device-visible: valid points a launch could not hold (PMArgs::refused)
     double *user_out = nullptr;         // caller-owned result arrays (bind_results)
     int32_t *user_ij = nullptr;
-    std::vector<Bucket> buckets;
-    // points beyond the launch classes of the one-workgroup-per-point kernels (search window too large for the LDS, template side
-    // above 64): each runs the large-window pipeline (pm_large.hip) after the launches of the others
-    std::vector<int32_t> large_idx;
-    DevBuf<int32_t> d_nan_idx;          // ... and, when NO other kernel of the run exists (template side above 64), the points without a valid window
-    int n_nan_idx = 0;
+    // the launches of the resident points for the current pair, the points of the large-window pipeline and the switches they
+    // were decided with (pm_plan.h; made by classify_points).  sid_pm_run launches from this and reads no switch of a plan again
+    Plan plan;
+    DevBuf<int32_t> d_nan_idx;          // Plan::nan_idx on the device
     sid::LwWorkspace lw;
     // rot_order 2..5: image 1 through scipy's spline prefilter (coef[1]; coef[0] = scratch), valid for (pair_serial, order); and the
     // templates of the resident points sampled from it (pre), valid for (pair_serial, points_serial)
@@ -139,7 +133,6 @@ struct sid_pm_ctx {
     int img_size = 0, n_angles = 0;
     uint32_t flags = 0;
     bool have_points = false;
-    double info[6] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -224,142 +217,12 @@ void make_samp2(const std::vector<uint16_t> &tab, int K, int s, std::vector<uint
     }
 }
 
-// window geometry of one point, the same arithmetic as the kernel (pmlib.py:200-202)
-// Workgroups of `lds` bytes that fit one CU.  gfx950 hands LDS out in 1280-byte granules (160 KB / 128;
-// measured with tools/ubench/lds_granule.hip: 53760 B -> 3 per CU, 53761 B -> 2).
-// workgroups of four wavefronts a CU takes at the kernels' register budget (3 wavefronts per SIMD): launch classes beyond
-// this differ in nothing.  The row-pair kernel's slot-group layouts (<= 7 angles) have a 128-VGPR build as well, for the
-// borders whose LDS footprint fits four times (SID_PM_NO_OCC4=1: off; A/B runs).
-constexpr bool kRecycleAllDefault = true;    // (round 6: -1.0 % on the 15-angle step, HBM traffic 12.7x -> 10.1x the algorithmic bytes: profiles/r06_ab_recycle_all.txt)
-constexpr int kMaxPerCu = 3;
-constexpr int kW3MaxLds = 40960;   // every window of pitch 104 that fits four times (borders 20 .. 23 at 34 / 35 px; measured per border: tools/archive/r4_w3.sh)
-// four workgroups per CU need the 128-VGPR build of the row-pair kernel (pm_kernel_rp_occ4.hip): the slot-group layouts only.
-// (Round 4 measured it for the full operand table as well - with sum w'^2 in global memory borders 20-26 fit four per CU:
-// border 20 +1.6 %, border 26 +5 % against three per CU with the sums in LDS; not shipped.)  SID_PM_NO_OCC4=1: never (A/B runs)
-// Four points per CU with three wavefronts per point (192 threads: 4 x 3 = the 12 wavefronts of 168 VGPRs a CU holds; pitch code
-// 1104: pm_kernel.h rp_pitch_is_w3) - the smallest windows only (SID_PM_W3_MAX_LDS: footprint up to which the class is used; SID_PM_NO_W3=1: never; A/B runs)
-int w3_max_lds() { const char *e = getenv("SID_PM_W3_MAX_LDS"); return getenv("SID_PM_NO_W3") ? 0 : e ? atoi(e) : kW3MaxLds; }
-int max_per_cu(bool rp, int rpp) { return (rp && (w3_max_lds() > 0 || (rpp > 0 && getenv("SID_PM_NO_OCC4") == nullptr))) ? 4 : kMaxPerCu; }
-
-int blocks_per_cu(int lds)
-{
-    constexpr int kLdsGranule = 1280;
-    const int granules = (lds + kLdsGranule - 1) / kLdsGranule;
-    return granules > 0 ? (sid::max_lds_bytes() / kLdsGranule) / granules : 8;
-}
-
-bool window_dims(double c2fg, double r2fg, double border, int s, int64_t rows2, int64_t cols2,
-                 int &wh, int &ww, bool *clipped = nullptr)
-{
-    const int hws = (int)((double)s / 2.0);
-    const double r0d = r2fg - hws - border, r1d = r2fg + hws + border + 1;
-    const double c0d = c2fg - hws - border, c1d = c2fg + hws + border + 1;
-    if (!(fabs(r0d) < 1e15 && fabs(r1d) < 1e15 && fabs(c0d) < 1e15 && fabs(c1d) < 1e15)) return false;
-    // NumPy slicing (pmlib.py:200-202): an end past the image is clipped to it; a start of -1 or less is not
-    // (NumPy would wrap it and the reference raises), nor is a window that leaves fewer than s + 1 rows or columns
-    const int64_t r0 = (int64_t)r0d, r1e = std::min((int64_t)r1d, rows2), c0 = (int64_t)c0d, c1e = std::min((int64_t)c1d, cols2);
-    if (!(r0 >= 0 && c0 >= 0 && r1e - r0 >= s + 1 && c1e - c0 >= s + 1))
-        return false;
-    wh = (int)(r1e - r0); ww = (int)(c1e - c0);
-    if (clipped) *clipped = (int64_t)r1d > rows2 || (int64_t)c1d > cols2;
-    return true;
-}
-
-// Launches of a SHORT run go side by side on the handle's side streams (sid_pm_run): all launches of the run together are at most
-// kSideRounds rounds of workgroups (SID_PM_SIDE_BY_SIDE=0 / 1: never / always; A/B runs).  ONE rule for the launcher and for
-// the estimate the shard cuts are made with (sid_pm_estimate_run_time).
-constexpr double kSideRounds = 16.0;
-bool side_by_side_rule(size_t n_launches, double rounds)
-{
-    if (n_launches < 2) return false;
-    const char *e = getenv("SID_PM_SIDE_BY_SIDE");
-    return e ? atoi(e) > 0 : rounds <= kSideRounds;
-}
-
 int check_images(const Image &a, const Image &b)
 {
     if (!a.ptr || !b.ptr) return fail(SID_PM_ERR_ARG, "null image pointer");
     if (a.rows < 1 || a.cols < 1 || a.stride < a.cols || b.rows < 1 || b.cols < 1 || b.stride < b.cols)
         return fail(SID_PM_ERR_ARG, "bad image shape/stride");
     return SID_PM_OK;
-}
-
-// paired: the kernel's two-row-phase sweep for angle sets of at most kPairedMaxAngles (pm_kernel.h)
-bool use_paired(int K)
-{
-    static const bool off = getenv("SID_PM_NO_PAIRED") != nullptr;                            // A/B runs
-    return K <= sid::kPairedMaxAngles && !off;
-}
-
-// row-pair kernel (pm_kernel_rp.inc): template sides 34 / 35, any number of angles.  (Up to 7 angles the classic kernel
-// pairs its slots - 8 output rows per item - and still loses to the row-pair kernel with half of its slots idle: 200x200
-// benchmark, 7 angles, mixed borders 4.59 vs 4.35 ms, border 20 3.28 vs 3.05, border 50 16.2 vs 14.8; 3 angles 4.52 vs 4.25.)
-// SID_PM_NO_RP (A/B runs and the tests of the classic kernel at these sizes) is read at every set_points / debug_point;
-// the decision is kept with the handle.
-bool use_rp(int s, int K)
-{
-    (void)K;
-    return sid::rp_size_supported(s) && getenv("SID_PM_NO_RP") == nullptr;
-}
-
-// row-pair kernel with at most 7 angles: paired slots (8 output rows per item with the 4-row kernel's registers; the LDS
-// layout is that of an 8-row band)
-int rp_paired(int K)
-{
-    if (K > sid::kPairedMaxAngles || getenv("SID_PM_NO_PAIRED") != nullptr) return 0;
-    return (K <= sid::kQuadMaxAngles && getenv("SID_PM_NO_QUAD") == nullptr) ? 2 : 1;   // (SID_PM_NO_QUAD: two groups also for <= 3 angles; A/B runs)
-}
-
-// band argument of rp_lds_layout: output rows per sweep work item
-int rp_rows(int rpp, int band) { return rpp == 2 ? 16 : rpp == 1 ? 8 : band; }
-
-// own_hes of rp_lds_layout: the general Hessian (hes_smth / mcc_norm, several groups of angles) keeps the magnitudes in LDS of
-// their own (as the kernel decides: pm_kernel_rp prologue)
-bool rp_own_hes(int K, uint32_t flags) { return K > sid::kRpGroup || (flags & (SID_PM_HES_SMTH | SID_PM_MCC_NORM)) != 0u; }
-
-// gs: sum w'^2 per placement in global memory (rp_lds_layout; decided per window shape by rp_use_gs, and what the kernel
-// instantiation of the launch's window pitch does: sid::rp_pitch_is_gs)
-int lds_need(bool rp, int rpp, int wh, int ww, int s, int K, uint32_t flags, int band = 4, int pitch = 0, bool gs = true)
-{
-    if (rp) return sid::rp_lds_layout(wh, ww, s, K <= sid::kRpGroup, rp_rows(rpp, band), sid::rp_pitch_bytes(pitch), sid::rp_tab_pitch(rpp), rp_own_hes(K, flags), gs).total;
-    return sid::mfma_lds_layout(wh, ww, s, band, use_paired(K) && band == 4).total;
-}
-
-// big layouts (rp_lds_layout): every per-placement table in the point's block of global memory; always the full-table 4-row kernel
-sid::RpLdsLayout big_layout(int wh, int ww, int s, int K, uint32_t flags)
-{
-    return sid::rp_lds_layout(wh, ww, s, K <= sid::kRpGroup, 4, 0, 512, rp_own_hes(K, flags), true, true);
-}
-
-// full-table row-pair launches with the sums in global memory also keep sum w' there (the winner then multiplies no all-ones
-// operand); decided when the blocks are sized (classify_points) and remembered for the launches (SID_PM_NO_GSI=1: off - A/B runs)
-bool gs_keep_si(const sid_pm_ctx *ctx) { return ctx->rp && ctx->gs_keep_si; }
-
-// Kept accumulators (PMArgs::gs_keep_acc, round 5): the gs launches of a run with ONE group of angles store the sweep's exact
-// S_IT' of every slot and placement in the point's block of global memory, and the winner's NCC matrix is a normalisation of
-// stored sums.  Default: the slot-group layouts (at most 7 angles - 16 / 32 bytes per placement; the reference's default is 3
-// angles); SID_PM_KEEP_ACC=1: also the full table (64 bytes per placement), =0: never (A/B runs and the tests of both routes).
-bool keep_acc_policy(bool rp, int rpp, int K)
-{
-    if (!rp || K > sid::kRpGroup) return false;
-    if (rpp == 0 && !sid::kKeepAccFull) return false;                  // (the full-table kernels carry the code in measurement builds only)
-    const char *e = getenv("SID_PM_KEEP_ACC");
-    return e ? atoi(e) > 0 : rpp > 0;
-}
-// ... per launch: four slot groups (at most 3 angles, 16 B per placement) everywhere; two groups (at most 7 angles, 32 B) only
-// in the four-per-CU class of the smallest windows - at larger borders the stores cost more than the winner's matrix
-// instructions they replace (7 angles, mixed borders: +1.5 % with, -2 % at border 20; SID_PM_KEEP_ACC=1 keeps them everywhere)
-bool keep_acc_launch(const sid_pm_ctx *ctx, bool gs, bool big, int cls)
-{
-    if (!ctx->gs_keep_acc || !gs || big) return false;
-    if (ctx->rp_paired == 1 && cls != 4) { const char *e = getenv("SID_PM_KEEP_ACC"); return e && atoi(e) > 0; }
-    return true;
-}
-// u32 entries of the block of a point of that shape in a gs launch
-uint32_t block_entries(const sid_pm_ctx *ctx, int wh, int ww, int band, bool keep)
-{
-    const int s = ctx->img_size;
-    return sid::rp_block_entries(wh - s + 1, ww - s + 1, rp_rows(ctx->rp_paired, band), 16 >> ctx->rp_paired, gs_keep_si(ctx), keep);
 }
 
 int check_sweep(int img_size, const double *angles, int n_angles, uint32_t flags)
@@ -385,7 +248,7 @@ void gauss_taps(double w5[5])
     for (int k = 0; k < 5; ++k) w5[k] = w[k] / sum;
 }
 
-int fill_args(sid_pm_ctx *ctx, sid::PMArgs &A)
+int fill_args(sid_pm_ctx *ctx, const Switches &run_sw, sid::PMArgs &A)
 {
     memset(&A, 0, sizeof A);
     gauss_taps(A.gauss_w);
@@ -400,284 +263,37 @@ int fill_args(sid_pm_ctx *ctx, sid::PMArgs &A)
     A.out_ij = ctx->user_out ? ctx->user_ij : ctx->out_ij.p;
     A.refused = ctx->h_refused;
     A.gsii = ctx->gsii.p; A.gsii_off = ctx->d_goff.p; A.rec = ctx->d_rec.p;
-    A.gs_keep_si = gs_keep_si(ctx) ? 1u : 0u;
-    A.gs_keep_acc = 0u; A.ring = nullptr; A.pool = ctx->pool.p; A.pool_stride = ctx->pool_stride;   // (per launch: sid_pm_run)
-    if (getenv("SID_PM_DEBUG_CHECK")) {
+    A.gs_keep_si = (ctx->rp && ctx->plan.gs_keep_si) ? 1u : 0u;
+    A.gs_keep_acc = 0u; A.ring = nullptr; A.pool = ctx->pool.p; A.pool_stride = ctx->plan.pool_stride;   // (per launch: sid_pm_run)
+    if (run_sw.debug_check) {
         if (!ctx->dbg_err.p && ctx->dbg_err.reserve(320) == SID_PM_OK) (void)hipMemset(ctx->dbg_err.p, 0, 320 * sizeof(int32_t));
         A.dbg_err = ctx->dbg_err.p;
     }
     return SID_PM_OK;
 }
 
-// Class of one window shape: band height of its sweep items, workgroups per CU, LDS bytes (natural window pitch) and - row-pair
-// kernel - whether sum w'^2 per placement lives in global memory (gs).  gs costs ~5 % where it changes nothing and buys
-// -10 .. -17 % where its smaller footprint lifts the shape into the next residency class, so it is chosen exactly there;
-// and wherever only a gs instantiation exists (window pitch above 112, the 8-row-band kernel, the run-time pitch).
-struct ShapeClass { bool gs; int band, cls, lds, nat_pitch; bool big = false; int w3_pitch = 0; };   // w3_pitch: pitch code of the three-wavefront class (0: not in it)   // big: cls 0, a launch of its own (one workgroup per CU)
-ShapeClass shape_class(bool rp, int rpp, int wh, int ww, int s, int K, uint32_t flags, bool band8_ok, bool force_gs)
-{
-    auto eval = [&](bool gs) {
-        ShapeClass c{gs, 4, 0, lds_need(rp, rpp, wh, ww, s, K, flags, 4, 0, gs), 0};
-        // the two-per-CU class runs the 8-row-band kernel (two wavefronts per SIMD leave it 256 VGPRs); its
-        // window carries a few more zero rows, and a point that then no longer fits twice joins the one-per-CU
-        // class (a launch of their own for the few points in between costs more than it saves)
-        if (band8_ok && blocks_per_cu(c.lds) == 2) {
-            const int need8 = lds_need(rp, rpp, wh, ww, s, K, flags, 8, 0, gs);
-            if (blocks_per_cu(need8) >= 2) { c.lds = need8; c.band = 8; c.cls = 2; }
-            else c.cls = 1;
-        } else c.cls = std::max(1, std::min(max_per_cu(rp, rpp), blocks_per_cu(c.lds)));
-        if (rp) c.nat_pitch = sid::rp_lds_layout(wh, ww, s, K <= sid::kRpGroup, rp_rows(rpp, c.band), 0, sid::rp_tab_pitch(rpp), rp_own_hes(K, flags), gs).wpitch;
-        return c;
-    };
-    if (!rp) return eval(false);
-    ShapeClass g = eval(true);
-    // (no four-per-CU build with gs - except the three-wavefront class of the full table, for the smallest windows)
-    // The three-wavefront class: window pitch 104 (borders 20 .. 23), sums in global memory, a footprint that fits four times.
-    // (Pitch 112 - borders 24 .. 28 - measured: full table +-0 / +0.5 / +4 %, three angles +1.5 / +-0 %, seven angles +1 %: not
-    // instantiated.  Sums in LDS - pitch code 2104, slot groups at borders 20 / 21 - won until the blocks of global memory held
-    // sum w' as well; since then the gs form is 1.5 % ahead there too and the code 2104 is no longer instantiated.)
-    if (K <= sid::kRpGroup && g.band == 4 && g.nat_pitch <= 104 && !force_gs) {
-        const int code = 1000 + sid::rp_class_pitch(g.nat_pitch), need = lds_need(rp, rpp, wh, ww, s, K, flags, 4, code, true);
-        if (need <= std::min(w3_max_lds(), 32 * 1280) && sid::rp_pitch_instantiated(4, rpp, code)) {
-            ShapeClass c = g; c.gs = true; c.cls = 4; c.lds = need; c.w3_pitch = code; return c;
-        }
-    }
-    g.cls = std::min(g.cls, 3);
-    if (g.lds > sid::max_lds_bytes() && getenv("SID_PM_NO_BIG") == nullptr) {   // beyond the LDS even so: the tables go to global memory
-        const sid::RpLdsLayout B = big_layout(wh, ww, s, K, flags);
-        if (B.total <= sid::max_lds_bytes()) return ShapeClass{true, 4, 0, B.total, B.wpitch, true};
-    }
-    if (force_gs || getenv("SID_PM_ALWAYS_GS") != nullptr) return g;
-    // slot groups: since their gs launches keep sum w' for the winner as well, the gs form is ahead at every border (3 / 7 angles,
-    // mixed: -0.9 %; borders 25 / 26: -0.8 %; tools/archive/r4_env_ab.sh) - unless the round-3 classes were asked for (SID_PM_NO_W3)
-    if (rpp > 0 && w3_max_lds() > 0 && getenv("SID_PM_NO_GS") == nullptr && getenv("SID_PM_NO_GSI") == nullptr) return g;
-    const ShapeClass l = eval(false);
-    if (l.band == 8 || l.nat_pitch > 112 || l.lds > sid::max_lds_bytes()) return g;   // (no instantiation without gs)
-    // a class the gs footprint reaches only pays where a kernel build exists for it: the four-per-CU build (128 VGPRs) is
-    // instantiated for the pitches without gs alone, so gs never buys the step from three to four
-    if (getenv("SID_PM_NO_GS") == nullptr && g.cls > l.cls) return g;
-    return l;
-}
-
-// Launch classes of the resident points for the pair that is current now: LDS footprint -> residency class
-// (workgroups per CU) -> one launch per (class, band), XCD-aware order inside.  The footprint depends on the shape
-// of image 2 (a window outside the image is a NaN point and gets the minimal footprint), so this runs in
-// set_points and again in run() whenever the current pair's image 2 has another shape.  Uploads `order`.
+// The plan of the resident points for the pair that is current now (pm_plan.h: plan_points, with the switches as the
+// environment holds them at this call) and its device side: buffers, free lists, the uploads of `order`, `goff` and the
+// point records.  The plan depends on the shape of image 2, so this runs in set_points and again in run() whenever the
+// current pair's image 2 has another shape.  The handle takes the plan only when all of it succeeded.
 int classify_points(sid_pm_ctx *ctx)
 {
-    const int64_t n = ctx->n;
-    const int s = ctx->img_size, K = ctx->n_angles;
-    const int64_t rows2 = ctx->cur[1].rows, cols2 = ctx->cur[1].cols;
-    const double *c2fg = ctx->h_c2fg.data(), *r2fg = ctx->h_r2fg.data(), *border = ctx->h_border.data();
-    static const bool no_band8 = getenv("SID_PM_NO_BAND8") != nullptr;                      // A/B runs
-    const bool rp = ctx->rp;
-    const int rpp = ctx->rp_paired;
-    const bool band8_ok = sid::mfma_band8_supported(s) && !no_band8 && (rp ? !ctx->rp_paired : !use_paired(K));   // (classic and row-pair kernels alike)
-    static const bool no_fixed_pitch = getenv("SID_PM_NO_FIXED_PITCH") != nullptr;         // (run-time pitch everywhere: gs instantiations; A/B runs)
-    // Everything the launch needs to know about a point follows from the SHAPE of its search window, and a run has a few
-    // dozen shapes (one per border): the LDS layouts are evaluated per shape, the points are only binned.
-    struct Shape { int wh, ww, lds, band, cls, nat_pitch, pitch; double work; std::vector<int32_t> idx; bool gs = false, big = false; int w3p = 0; bool keep = false; bool large = false; bool pooled = false; };
-    std::vector<Shape> shapes;
-    std::vector<int32_t> slot_of((size_t)1 << 16, -1);                // (wh, ww) -> shape, direct-mapped on a hash of the pair
-    auto find_shape = [&](int wh, int ww) -> int {
-        uint32_t h = ((uint32_t)wh * 2654435761u ^ (uint32_t)ww * 40503u) & 0xffffu;
-        for (;; h = (h + 1) & 0xffffu) {
-            const int k = slot_of[h];
-            if (k < 0) { slot_of[h] = (int32_t)shapes.size(); return -1 - (int)h; }
-            if (shapes[(size_t)k].wh == wh && shapes[(size_t)k].ww == ww) return k;
-        }
-    };
-    ctx->gs_keep_si = getenv("SID_PM_NO_GSI") == nullptr;
-    ctx->gs_keep_acc = keep_acc_policy(rp, rpp, K);
-    const uint32_t flags = ctx->flags;
-    // template sides the one-point kernels do not take: every point with a valid window runs the large-window pipeline
-    const bool small_ok = sid::mfma_img_size_supported(s);
-    ctx->large_idx.clear(); ctx->n_nan_idx = 0;
-    const int lds_min = small_ok ? lds_need(rp, rpp, s + 1, s + 1, s, K, flags, 4, 0, false) : 0;
-    {   // shape 0: points whose window does not lie inside image 2 (they write NaN at once; minimal footprint)
-        Shape z{0, 0, lds_min, 4, std::min(kMaxPerCu, blocks_per_cu(lds_min)), 0, 0, 0.0, {}};   // (NaN writers: any class)
-        shapes.push_back(z);
-    }
-    double macs = 0, bytes = 0, valid = 0;
-    int lds_max = lds_min;
-    std::map<std::pair<int, int>, int> clipped_shape;                // windows clipped by the edge of image 2: (wh, ww) -> shape
-    std::vector<int32_t> shape_of((size_t)n, 0);                      // shape of every point (0: its window does not lie inside image 2)
-    for (int64_t i = 0; i < n; ++i) {
-        int wh = 0, ww = 0;
-        bool clipped = false;
-        if (!window_dims(c2fg[i], r2fg[i], border[i], s, rows2, cols2, wh, ww, &clipped)) { shapes[0].idx.push_back((int32_t)i); continue; }
-        if (wh > 65535 || ww > 4000000) return fail(SID_PM_ERR_UNSUPPORTED, "point %lld: search window %dx%d too large (65535 rows: a launch dimension of the large-window pipeline)", (long long)i, wh, ww);
-        // a window clipped by the bottom / right edge of image 2 (NumPy slicing) has a shape the one-point kernels' layouts were
-        // not validated for (as few as two placement rows or columns next to a full-width other axis): such points run the
-        // large-window pipeline, whose kernels take any rectangle byte by byte (the benchmark grid never reaches an edge)
-        // (one shape per clipped wh x ww, kept apart from the one-point kernels' shapes of the same size; the pipeline itself runs
-        // all of its points as one batch of launches - run_large_points)
-        int k = -1;
-        if (clipped) {
-            const auto it = clipped_shape.find(std::make_pair(wh, ww));
-            if (it != clipped_shape.end()) k = it->second;
-        } else {
-            k = find_shape(wh, ww);
-        }
-        if (clipped && k < 0) {
-            Shape sh{wh, ww, 0, 4, 0, 0, 0, 0.0, {}};
-            sh.large = true;
-            sh.work = (double)(wh - s + 1) * (double)(ww - s + 1);
-            k = (int)shapes.size();
-            clipped_shape.emplace(std::make_pair(wh, ww), k);
-            shapes.push_back(sh);
-        } else if (k < 0) {
-            Shape sh{wh, ww, 0, 4, 0, 0, 0, 0.0, {}};
-            ShapeClass sc{false, 4, 1, 0, 0};
-            if (small_ok) sc = shape_class(rp, rpp, wh, ww, s, K, flags, band8_ok, no_fixed_pitch);
-            // a window whose tables do not fit the LDS of one workgroup: the placement space is tiled over the device instead
-            if (!small_ok || sc.lds > sid::max_lds_bytes() || getenv("SID_PM_ALL_LARGE") != nullptr) { sh.large = true; sc = ShapeClass{false, 4, 1, 0, 0}; }
-            sh.lds = sc.lds; sh.band = sc.band; sh.cls = sc.cls; sh.gs = sc.gs; sh.nat_pitch = sc.nat_pitch; sh.big = sc.big; sh.w3p = sc.w3_pitch;
-            sh.work = (double)(wh - s + 1) * (double)(ww - s + 1);
-            k = (int)shapes.size();
-            shapes.push_back(sh);
-        }
-        Shape &sh = shapes[(size_t)k];
-        if (sh.large) ctx->large_idx.push_back((int32_t)i);
-        else sh.idx.push_back((int32_t)i);
-        shape_of[(size_t)i] = (int32_t)k;
-        macs += (double)K * sh.work * s * s;
-        // window + bounding box of the rotated template + 5 inputs + outputs
-        bytes += (double)wh * ww + 51.0 * 51.0 + 40.0 + 52.0;
-        valid += 1;
-    }
-    if (!small_ok) {                                                  // no one-point kernel of this template side: the NaN rows are written by lw_write_nan
-        ctx->n_nan_idx = (int)shapes[0].idx.size();
-        if (int rc = ctx->d_nan_idx.reserve(std::max<size_t>(shapes[0].idx.size(), 1))) return rc;
-        if (ctx->n_nan_idx) HIP_TRY(hipMemcpy(ctx->d_nan_idx.p, shapes[0].idx.data(), sizeof(int32_t) * shapes[0].idx.size(), hipMemcpyHostToDevice));
-        shapes[0].idx.clear();
-    }
-    // launch order of the shapes: biggest footprints (fewest workgroups per CU) first, one launch per (class, band), longest first
-    std::vector<int> ord;
-    for (size_t k = 0; k < shapes.size(); ++k) if (!shapes[k].idx.empty()) ord.push_back((int)k);
-    std::sort(ord.begin(), ord.end(), [&](int a, int b) {
-        const Shape &x = shapes[(size_t)a], &y = shapes[(size_t)b];
-        if (x.cls != y.cls) return x.cls < y.cls;
-        if (x.band != y.band) return x.band < y.band;
-        if (x.gs != y.gs) return x.gs;                                // (gs first: the larger windows of a class)
-        if (x.w3p != y.w3p) return x.w3p > y.w3p;                     // (three-wavefront class: one launch per window pitch)
-        if (x.work != y.work) return x.work > y.work;
-        return x.idx[0] < y.idx[0];
-    });
-    // Row-pair kernel: one window pitch per launch, a compile-time constant of the kernel instantiation (every LDS offset of
-    // the sweep's and the winner's fragment loops is then an immediate).  The pitch of a launch = the smallest instantiated
-    // pitch that holds the natural pitch of all of its points; if a footprint with that pitch no longer fits its residency
-    // class, the whole launch keeps the run-time pitch (SID_PM_NO_FIXED_PITCH=1: always; A/B runs).
-    // gs groups take a pitch of 136 or more (or the run-time pitch): those instantiations keep sum w'^2 in global memory.
-    if (rp) {
-        for (size_t a = 0; a < ord.size();) {
-            size_t b = a + 1;
-            const Shape &first = shapes[(size_t)ord[a]];
-            while (b < ord.size() && shapes[(size_t)ord[b]].cls == first.cls && shapes[(size_t)ord[b]].band == first.band &&
-                   shapes[(size_t)ord[b]].gs == first.gs && shapes[(size_t)ord[b]].w3p == first.w3p) ++b;
-            const bool gs = first.gs;
-            int nat = gs ? 136 : 0;
-            for (size_t i = a; i < b; ++i) nat = std::max(nat, shapes[(size_t)ord[i]].nat_pitch);
-            int pitch = (nat > 0 && !no_fixed_pitch && !first.big) ? sid::rp_class_pitch(nat) : 0;
-            if (first.w3p) pitch = first.w3p;                                  // (the three-wavefront class: its own instantiations)
-            if (pitch && !sid::rp_pitch_instantiated(first.band, rpp, pitch)) pitch = 0;
-            for (size_t i = a; i < b && pitch; ++i) {
-                const Shape &sh = shapes[(size_t)ord[i]];
-                if (sh.wh > 0 && std::min(max_per_cu(rp, rpp), blocks_per_cu(lds_need(rp, rpp, sh.wh, sh.ww, s, K, flags, sh.band, pitch, gs))) < first.cls) pitch = 0;
-            }
-            // (a group without gs that lost its compile-time pitch - it does not happen with the instantiated pitches - runs the
-            // run-time-pitch kernel, which is a gs one)
-            const bool gs_now = gs || pitch == 0;
-            for (size_t i = a; i < b; ++i) {
-                Shape &sh = shapes[(size_t)ord[i]];
-                sh.pitch = pitch; sh.gs = gs_now;
-                if (sh.wh > 0 && !sh.big) sh.lds = lds_need(rp, rpp, sh.wh, sh.ww, s, K, flags, sh.band, pitch, gs_now);
-            }
-            a = b;
-        }
-    }
-    for (Shape &sh : shapes) sh.keep = rp && sh.wh > 0 && keep_acc_launch(ctx, sh.gs, sh.big, sh.cls);   // (the launch class is final here)
-    // Recycled blocks (PMArgs::ring): the launches that keep accumulators always (their blocks are 3 - 5x larger); the others that
-    // keep per-placement tables in global memory with SID_PM_RECYCLE_ALL != 0 (SID_PM_NO_RECYCLE=1: a block per launch position everywhere)
-    {
-        const bool recycle = getenv("SID_PM_NO_RECYCLE") == nullptr;
-        const char *ra = getenv("SID_PM_RECYCLE_ALL");
-        const bool recycle_all = ra ? atoi(ra) != 0 : kRecycleAllDefault;
-        for (Shape &sh : shapes) sh.pooled = rp && sh.wh > 0 && sh.gs && !sh.big && recycle && (sh.keep || recycle_all);
-    }
-    // XCD-aware launch order.  Workgroup j of a launch runs on XCD j mod 8 and every XCD has its own L2, so
-    // within a run of points of equal class and work (= equal border: the order there is the caller's, i.e.
-    // spatial for a grid) the run is cut into 8 contiguous chunks and chunk c goes to the XCD of slot
-    // (start + c) mod 8: neighbouring points - whose search windows overlap - meet in the same L2.
-    // Runs keep their place in the launch (long first), so the load balance across XCDs is unchanged.
-    static const bool no_xcd = getenv("SID_PM_NO_XCD_ORDER") != nullptr;                         // A/B runs
-    std::vector<int32_t> order;
-    order.reserve((size_t)n);
-    ctx->buckets.clear();
-    std::vector<int32_t> run;
-    for (size_t a = 0; a < ord.size();) {
-        // a run = the shapes of equal (class, band, work): their points in the caller's order
-        size_t b = a + 1;
-        const Shape &first = shapes[(size_t)ord[a]];
-        while (b < ord.size() && shapes[(size_t)ord[b]].cls == first.cls && shapes[(size_t)ord[b]].band == first.band &&
-               shapes[(size_t)ord[b]].pitch == first.pitch && shapes[(size_t)ord[b]].work == first.work) ++b;
-        const std::vector<int32_t> *src = &first.idx;
-        if (b - a > 1) {
-            run.clear();
-            for (size_t i = a; i < b; ++i) run.insert(run.end(), shapes[(size_t)ord[i]].idx.begin(), shapes[(size_t)ord[i]].idx.end());
-            std::sort(run.begin(), run.end());
-            src = &run;
-        }
-        int lds_run = 0;
-        for (size_t i = a; i < b; ++i) lds_run = std::max(lds_run, shapes[(size_t)ord[i]].lds);
-        lds_max = std::max(lds_max, lds_run);
-        if (ctx->buckets.empty() || ctx->buckets.back().band != first.band || ctx->buckets.back().pitch != first.pitch ||
-            ctx->info[5] != (double)first.cls)
-            ctx->buckets.push_back(Bucket{(int)order.size(), 0, 0, first.band, first.pitch,
-                                          (rp && first.cls >= 4 && sid::rp_pitch_instantiated(first.band, rpp, first.pitch, 4)) ? 4 : 3});
-        ctx->info[5] = (double)first.cls;                             // (class of the bucket being filled)
-        Bucket &bk = ctx->buckets.back();
-        bk.big = first.big; bk.keep = first.keep; bk.pooled = first.pooled;
-        bk.count += (int)src->size();
-        bk.lds = std::max(bk.lds, lds_run);
-        if (rp && first.gs)                                           // (launches that keep sum w'^2 in global memory: the largest block)
-            for (size_t i = a; i < b; ++i) {
-                const Shape &sh = shapes[(size_t)ord[i]];
-                if (sh.wh > 0) bk.gs_stride = std::max<uint32_t>(bk.gs_stride, sh.big ? (uint32_t)(big_layout(sh.wh, sh.ww, s, K, flags).big_bytes / 4)
-                                                                                      : block_entries(ctx, sh.wh, sh.ww, sh.band, sh.keep));
-            }
-        constexpr int64_t kXcd = 8;
-        const int64_t L = (int64_t)src->size(), m = (L + kXcd - 1) / kXcd;
-        if (!no_xcd && L >= 4 * kXcd) {
-            for (int64_t p = 0; p < m; ++p)                           // slot t = p * 8 + c takes element c * m + p
-                for (int64_t c = 0; c < kXcd; ++c) {
-                    const int64_t e = c * m + p;
-                    if (e < L) order.push_back((*src)[(size_t)e]);
-                }
-        } else order.insert(order.end(), src->begin(), src->end());
-        a = b;
-    }
-    // row-pair kernel: every launch position of a launch that keeps per-placement tables in global memory (gs and big launches)
-    // gets a block of its own there, in 256-byte granules: sum w'^2, then sum w' or the sweep's accumulators (block_entries);
-    // big layouts: every table of the point.  Points whose launch keeps its sums in LDS get none.  Scratch per run =
-    // the sum over those points: 14 KB per point at border 20 with sum w', 48 KB with the accumulators of four slot groups,
-    // 0.6 MB at border 111 (sid_pm.h).
-    std::vector<uint32_t> goff;
-    uint64_t gsii_granules = 0;
-    if (rp) {
-        // Launches that keep accumulators take their blocks from the per-XCD free lists (PMArgs::ring): kPoolBlocks blocks (1024 per
-        // XCD) of the largest such block, whatever the number of points (SID_PM_NO_RECYCLE=1: a block per launch position, as the others)
-        uint32_t stride = 0;
-        std::vector<uint32_t> gran_shape(shapes.size(), 0u);
-        for (size_t k = 1; k < shapes.size(); ++k) {
-            const Shape &sh = shapes[k];
-            if (sh.big) gran_shape[k] = (uint32_t)(big_layout(sh.wh, sh.ww, s, K, flags).big_bytes / 256);
-            else if (sh.pooled) stride = std::max(stride, block_entries(ctx, sh.wh, sh.ww, sh.band, sh.keep));
-            else if (sh.gs) gran_shape[k] = block_entries(ctx, sh.wh, sh.ww, sh.band, sh.keep) / 64u;
-        }
-        ctx->pool_stride = stride;
-        if (stride) {
-            if (int rc = ctx->pool.reserve((size_t)sid::kPoolBlocks * stride)) return rc;
+    const Switches sw = read_switches();
+    PlanInput in;
+    in.n = ctx->n;
+    in.c1 = ctx->h_c1.data(); in.r1 = ctx->h_r1.data(); in.c2fg = ctx->h_c2fg.data(); in.r2fg = ctx->h_r2fg.data(); in.border = ctx->h_border.data();
+    in.s = ctx->img_size; in.K = ctx->n_angles; in.flags = ctx->flags;
+    in.rows1 = ctx->cur[0].rows; in.cols1 = ctx->cur[0].cols; in.rows2 = ctx->cur[1].rows; in.cols2 = ctx->cur[1].cols;
+    in.rp = ctx->rp; in.rpp = ctx->rp_paired;
+    Plan plan;
+    std::string err;
+    if (int rc = plan_points(in, sw, plan, err)) return fail(rc, "%s", err.c_str());
+    const size_t n_order = plan.order.size();
+    if (int rc = ctx->d_nan_idx.reserve(std::max<size_t>(plan.nan_idx.size(), 1))) return rc;
+    if (!plan.nan_idx.empty()) HIP_TRY(hipMemcpy(ctx->d_nan_idx.p, plan.nan_idx.data(), sizeof(int32_t) * plan.nan_idx.size(), hipMemcpyHostToDevice));
+    if (ctx->rp) {
+        if (plan.pool_stride) {
+            if (int rc = ctx->pool.reserve((size_t)sid::kPoolBlocks * plan.pool_stride)) return rc;
             if (int rc = ctx->ring.reserve((size_t)sid::kRingU64 * 2)) return rc;
             // every block free (all bits set).  Rewritten at every classification - no launch of this handle is in flight here -
             // so that an aborted run cannot leave a list short of blocks
@@ -686,52 +302,33 @@ int classify_points(sid_pm_ctx *ctx)
             HIP_TRY(hipMemcpyAsync(ctx->ring.p, init.data(), init.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
         }
-        goff.resize(order.size());
-        for (int64_t p = 0; p < (int64_t)order.size(); ++p) {
-            goff[(size_t)p] = (uint32_t)gsii_granules;
-            gsii_granules += gran_shape[(size_t)shape_of[(size_t)order[(size_t)p]]];
-        }
-        if (gsii_granules >= 0xffffffffull) return fail(SID_PM_ERR_UNSUPPORTED, "per-placement tables in global memory beyond 1 TB");
         {   // fail with the numbers before hipMalloc does
             size_t free_b = 0, total_b = 0;
-            if (gsii_granules * 256ull > ctx->gsii.cap * sizeof(uint32_t) && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-                gsii_granules * 256ull > (uint64_t)free_b + ctx->gsii.cap * sizeof(uint32_t))
+            if (plan.gsii_granules * 256ull > ctx->gsii.cap * sizeof(uint32_t) && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+                plan.gsii_granules * 256ull > (uint64_t)free_b + ctx->gsii.cap * sizeof(uint32_t))
                 return fail(SID_PM_ERR_NOMEM, "per-placement tables of %lld points need %.1f GB of device memory, %.1f GB are free (smaller batches, or borders below 69 px)",
-                            (long long)n, (double)gsii_granules * 256e-9, (double)free_b * 1e-9);
+                            (long long)ctx->n, (double)plan.gsii_granules * 256e-9, (double)free_b * 1e-9);
         }
-        if (int rc = ctx->gsii.reserve((size_t)std::max<uint64_t>(gsii_granules, 1) * 64)) return rc;
-        if (int rc = ctx->d_goff.reserve((size_t)std::max<int64_t>(n, 1))) return rc;
-        if (int rc = ctx->d_rec.reserve((size_t)std::max<int64_t>(n, 1))) return rc;
+        if (int rc = ctx->gsii.reserve((size_t)std::max<uint64_t>(plan.gsii_granules, 1) * 64)) return rc;
+        if (int rc = ctx->d_goff.reserve((size_t)std::max<int64_t>(ctx->n, 1))) return rc;
+        if (int rc = ctx->d_rec.reserve((size_t)std::max<int64_t>(ctx->n, 1))) return rc;
     }
-    std::vector<sid::PointRec> recs;
-    if (rp) {
-        const double *c1v = ctx->h_c1.data(), *r1v = ctx->h_r1.data();
-        recs.resize(order.size());
-        for (int64_t p = 0; p < (int64_t)order.size(); ++p) {
-            const int32_t i = order[(size_t)p];
-            recs[(size_t)p] = sid::PointRec{i, goff[(size_t)p], c1v[i], r1v[i], c2fg[i], r2fg[i], border[i]};
-        }
+    if (n_order) {                                                    // (the points of the large-window pipeline are in no launch)
+        HIP_TRY(hipMemcpyAsync(ctx->d_order, plan.order.data(), sizeof(int32_t) * n_order, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->rp) HIP_TRY(hipMemcpyAsync(ctx->d_goff.p, plan.goff.data(), sizeof(uint32_t) * n_order, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->rp) HIP_TRY(hipMemcpyAsync(ctx->d_rec.p, plan.recs.data(), sizeof(sid::PointRec) * n_order, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));               // (the host vectors are pageable)
     }
-    if (!order.empty()) {                                             // (the points of the large-window pipeline are in no launch)
-        HIP_TRY(hipMemcpyAsync(ctx->d_order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, ctx->stream));
-        if (rp) HIP_TRY(hipMemcpyAsync(ctx->d_goff.p, goff.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, ctx->stream));
-        if (rp) HIP_TRY(hipMemcpyAsync(ctx->d_rec.p, recs.data(), sizeof(sid::PointRec) * order.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));               // `order` and `goff` are locals
-    }
-    if (getenv("SID_PM_VERBOSE") != nullptr)                          // the launches of a step, one line each
-        for (const Bucket &b : ctx->buckets)
+    if (sw.verbose) {                                                 // the launches of a step, one line each
+        for (const Bucket &b : plan.buckets)
             fprintf(stderr, "sid_pm: launch of %d points, %d B of LDS (%d per CU), band %d, window pitch %d, %d wavefronts per SIMD\n",
                     b.count, b.lds, std::min(b.occ, blocks_per_cu(b.lds)), b.band, b.pitch, b.occ);
-    if (getenv("SID_PM_VERBOSE") != nullptr && !ctx->large_idx.empty())
-        fprintf(stderr, "sid_pm: %zu points through the large-window pipeline (one point at a time, tiled over the device)\n", ctx->large_idx.size());
-    ctx->cls_rows2 = rows2; ctx->cls_cols2 = cols2;
-    const double img_bytes = (double)ctx->cur[0].rows * ctx->cur[0].cols + (double)rows2 * cols2;
-    ctx->info[0] = (double)ctx->buckets.size();
-    ctx->info[1] = valid;
-    ctx->info[2] = macs;
-    ctx->info[3] = std::min(bytes, img_bytes + 92.0 * valid);
-    ctx->info[4] = (double)lds_max;
-    ctx->info[5] = 0;
+        if (!plan.large_idx.empty())
+            fprintf(stderr, "sid_pm: %zu points through the large-window pipeline (one point at a time, tiled over the device)\n", plan.large_idx.size());
+    }
+    ctx->plan = std::move(plan);
+    ctx->plan.recs = std::vector<sid::PointRec>();                    // (on the device now; the largest of the host vectors)
+    ctx->cls_rows2 = in.rows2; ctx->cls_cols2 = in.cols2;
     return SID_PM_OK;
 }
 
@@ -783,14 +380,14 @@ int ensure_presampled(sid_pm_ctx *ctx, int order)
 // (pm_large.hip): a stream of launches, nothing read back; results straight into the rows of the run's result arrays.
 int run_large_points(sid_pm_ctx *ctx, const sid::PMArgs &A)
 {
-    if (ctx->n_nan_idx) {
-        const int e = sid::lw_write_nan(ctx->d_nan_idx.p, ctx->n_nan_idx, A.out, A.out_ij, ctx->stream);
+    if (!ctx->plan.nan_idx.empty()) {
+        const int e = sid::lw_write_nan(ctx->d_nan_idx.p, (int)ctx->plan.nan_idx.size(), A.out, A.out_ij, ctx->stream);
         if (e) return fail(SID_PM_ERR_HIP, "large-window pipeline: %s", hipGetErrorString((hipError_t)e));
     }
     std::vector<sid::LargeCall> calls;
-    calls.reserve(ctx->large_idx.size());
+    calls.reserve(ctx->plan.large_idx.size());
     size_t worst = 0;
-    for (const int32_t i : ctx->large_idx) {
+    for (const int32_t i : ctx->plan.large_idx) {
         int wh = 0, ww = 0;
         const double c2 = ctx->h_c2fg[(size_t)i], r2 = ctx->h_r2fg[(size_t)i], b = ctx->h_border[(size_t)i];
         if (!window_dims(c2, r2, b, ctx->img_size, ctx->cur[1].rows, ctx->cur[1].cols, wh, ww)) continue;   // (cannot happen: classified with this pair)
@@ -986,6 +583,7 @@ SID_EXPORT int sid_pm_set_points(sid_pm_ctx *ctx, const double *c1, const double
     if (!ctx->have_pair) return fail(SID_PM_ERR_STATE, "set_points needs an image pair (upload_pair/bind_pair first)");
     Guard g(ctx->device);
     const int s = img_size, K = n_angles;
+    const Switches sw = read_switches();
 
     (void)alpha0;
     std::vector<double> rotv;
@@ -993,11 +591,11 @@ SID_EXPORT int sid_pm_set_points(sid_pm_ctx *ctx, const double *c1, const double
     std::vector<uint16_t> sampv;
     int nflag = 0;
     // (rot_order = 1: no offset table - every template sample is interpolated in float64 by the general sampler)
-    if (!getenv("SID_PM_NO_SAMP_TABLE") && ((flags >> 3) & 7u) == 0u && sid::mfma_img_size_supported(s)) nflag = make_samp(rotv, K, s, sampv);
+    if (!sw.no_samp_table && ((flags >> 3) & 7u) == 0u && sid::mfma_img_size_supported(s)) nflag = make_samp(rotv, K, s, sampv);
     std::vector<uint32_t> samp2v;
     // (measured +2 % on the 15-angle step - fifteen table loads per angle instead of five, a uniform branch per chunk - although
     // it executes a third fewer VALU instructions in the template phase: built on request only, SID_PM_SAMP2=1)
-    if (!sampv.empty() && use_rp(s, K) && getenv("SID_PM_SAMP2") != nullptr) make_samp2(sampv, K, s, samp2v);
+    if (!sampv.empty() && use_rp(sw, s) && sw.samp2) make_samp2(sampv, K, s, samp2v);
 
     // one arena, one upload: [5n doubles | K angles | 4K rotation terms | order (int32 n) | sampling table]
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -1028,7 +626,7 @@ SID_EXPORT int sid_pm_set_points(sid_pm_ctx *ctx, const double *c1, const double
     ctx->h_c1.assign(c1, c1 + n); ctx->h_r1.assign(r1, r1 + n);
 
     ctx->user_out = nullptr; ctx->user_ij = nullptr;
-    ctx->n = n; ctx->img_size = s; ctx->n_angles = K; ctx->flags = flags; ctx->rp = use_rp(s, K); ctx->rp_paired = ctx->rp ? rp_paired(K) : 0;
+    ctx->n = n; ctx->img_size = s; ctx->n_angles = K; ctx->flags = flags; ctx->rp = use_rp(sw, s); ctx->rp_paired = ctx->rp ? rp_paired(sw, K) : 0;
     ctx->have_points = false;
     ++ctx->points_serial;
     if (int rc = classify_points(ctx)) return rc;
@@ -1056,32 +654,34 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (int rc = classify_points(ctx)) return rc;
     }
+    const Switches run_sw = read_switches();                          // (the four switches of a run: side_by_side, side_first, verbose, debug_check)
+    const std::vector<Bucket> &buckets = ctx->plan.buckets;
     sid::PMArgs A;
-    fill_args(ctx, A);
+    fill_args(ctx, run_sw, A);
     if (ctx->cur_slot >= 0 && ctx->ready_rec[ctx->cur_slot])
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->slot_ready[ctx->cur_slot], 0));
     {   // rot_order 2..5: spline coefficients of image 1 (once per pair), templates of the points sampled from them (once per pair and point set)
         const int order = (int)((ctx->flags >> 3) & 7u);
         if (int rc = ensure_coef(ctx, order)) return rc;
-        if (!ctx->buckets.empty()) { if (int rc = ensure_presampled(ctx, order)) return rc; }
-        A.pre = (order >= 2 && !ctx->buckets.empty()) ? ctx->pre.p : nullptr;
+        if (!buckets.empty()) { if (int rc = ensure_presampled(ctx, order)) return rc; }
+        A.pre = (order >= 2 && !buckets.empty()) ? ctx->pre.p : nullptr;
     }
     // Launches side by side for SHORT runs.  A full grid is dozens of rounds of workgroups per launch and its launches run one
     // after the other (side by side they measured 1-6 % slower: a CU that took a workgroup of a large-window class is lost to
     // several small ones, rounds 2-4).  A rank's shard of an 8-GPU run is two or three launches of one to seven rounds each,
     // and every launch ends with a half-empty round - a quarter of such a run; side by side the next launch's workgroups fill
     // the CUs the previous one drains.  Rule: all launches of a run together are at most kSideRounds rounds of workgroups
-    // (SID_PM_SIDE_BY_SIDE=0 / 1: never / always; A/B runs).  The launches keep their order (largest footprint first).
+    // (side_by_side_rule).  The launches keep their order (largest footprint first).
     bool side_by_side = false;
-    if (ctx->buckets.size() > 1) {
+    if (buckets.size() > 1) {
         double rounds = 0;
-        for (const Bucket &b : ctx->buckets) rounds += (double)b.count / (256.0 * std::max(1, std::min(b.band == 8 ? 2 : 4, blocks_per_cu(b.lds))));
-        side_by_side = side_by_side_rule(ctx->buckets.size(), rounds);
+        for (const Bucket &b : buckets) rounds += (double)b.count / (256.0 * launch_shape(b, ctx->rp).round_slots);
+        side_by_side = side_by_side_rule(run_sw, buckets.size(), rounds);
     }
-    // (SID_PM_SIDE_FIRST=n, experiments: only the first n launches of a long run side by side - the large-window classes, a
+    // (Switches::side_first, experiments: only the first n launches of a long run side by side - the large-window classes, a
     // round or two of workgroups each - then the rest in sequence)
-    int n_side = side_by_side ? (int)ctx->buckets.size() : 0;
-    if (!side_by_side) if (const char *e = getenv("SID_PM_SIDE_FIRST")) n_side = std::min((int)ctx->buckets.size(), std::max(0, atoi(e)));
+    int n_side = side_by_side ? (int)buckets.size() : 0;
+    if (!side_by_side && run_sw.side_first >= 0) n_side = std::min((int)buckets.size(), run_sw.side_first);
     if (n_side > 1) HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
     int nb = 0;
     unsigned used = 0;
@@ -1094,7 +694,7 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         used = 0;
         return SID_PM_OK;
     };
-    for (const Bucket &b : ctx->buckets) {
+    for (const Bucket &b : buckets) {
         // launch k of a side-by-side run: the handle's stream, then the side streams in turn
         hipStream_t st = ctx->stream;
         if (nb == n_side && n_side > 1) { if (int rc = join()) return rc; }
@@ -1110,18 +710,13 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         A.rec = ctx->d_rec.p ? ctx->d_rec.p + b.offset : nullptr;
         A.n_launch = b.count;
         A.gs_keep_acc = b.keep ? 1u : 0u;
-        A.ring = (b.pooled && ctx->pool_stride) ? ctx->ring.p : nullptr;
+        A.ring = (b.pooled && ctx->plan.pool_stride) ? ctx->ring.p : nullptr;
         const int lds_launch = std::min(b.lds, sid::max_lds_bytes());
         A.lds_bytes = lds_launch;
-        // 256 threads per point; 768 when the LDS footprint leaves room for one point per CU only, so that
-        // the CU still carries 12 wavefronts (3 per SIMD = the register budget).  (Measured for the
-        // two-per-CU class, border 28: 256 threads 5.8 ms, 384: 9.1, 512: 7.8, 768: 7.8 - six wavefronts per group
-        // land 2/2/1/1 on the SIMDs, a second group of 168-VGPR wavefronts then no longer fits.)
-        const int per_cu = std::max(1, std::min(b.band == 8 ? 2 : 8, blocks_per_cu(b.lds)));
-        const int nthreads = b.band == 8 ? 256 : (per_cu == 1 ? 768 : (ctx->rp && sid::rp_pitch_is_w3(b.pitch)) ? 192 : 256);
+        const int nthreads = launch_shape(b, ctx->rp).nthreads;
         const int e = ctx->rp
                           ? sid::launch_pm_rp(A, lds_launch, nthreads, b.band, b.big ? 0 : ctx->rp_paired, b.pitch, b.occ, st, b.big)
-                          : sid::launch_pm_mfma(A, lds_launch, nthreads, b.band, use_paired(ctx->n_angles), st);
+                          : sid::launch_pm_mfma(A, lds_launch, nthreads, b.band, use_paired(ctx->plan.sw, ctx->n_angles), st);
         if (e != 0) {
             (void)join();                                            // (what the side streams already hold still orders before the handle's stream)
             return fail(SID_PM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -1145,7 +740,7 @@ SID_EXPORT int sid_pm_check(sid_pm_ctx *ctx)
     if (!ctx->h_refused) return SID_PM_OK;
     const int32_t n = __atomic_exchange_n(ctx->h_refused, 0, __ATOMIC_ACQ_REL);
     const int32_t polls = __atomic_exchange_n(ctx->h_refused + 1, 0, __ATOMIC_ACQ_REL);
-    if (polls > 0 && getenv("SID_PM_VERBOSE") != nullptr) fprintf(stderr, "sid_pm: %d workgroup(s) found the home words of their XCD's free list empty and took a block of its reserve words\n", (int)polls);
+    if (polls > 0 && read_switches().verbose) fprintf(stderr, "sid_pm: %d workgroup(s) found the home words of their XCD's free list empty and took a block of its reserve words\n", (int)polls);
     if (n != 0)
         return fail(SID_PM_ERR_STATE, "%d grid point(s) with a valid search window were refused by their launch (LDS layout of the "
                                       "kernel and classification of the host disagree, or all %d recycled blocks of global memory of an XCD "
@@ -1239,7 +834,8 @@ SID_EXPORT int sid_pm_work_info(sid_pm_ctx *ctx, double info[6])
 {
     if (!ctx || !info) return fail(SID_PM_ERR_ARG, "null argument");
     if (!ctx->have_points) return fail(SID_PM_ERR_STATE, "work_info before set_points");
-    memcpy(info, ctx->info, sizeof ctx->info);
+    memcpy(info, ctx->plan.info, sizeof ctx->plan.info);
+    info[5] = 0;
     return SID_PM_OK;
 }
 
@@ -1404,12 +1000,13 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
     if (int rc = check_sweep(img_size, angles, n_angles, flags)) return rc;
     Guard g(ctx->device);
     const int s = img_size, K = n_angles;
-    const bool rp = use_rp(s, K);
-    const int rpp = rp ? rp_paired(K) : 0;
-    int wh = 0, ww = 0, lds = lds_need(rp, rpp, s + 1, s + 1, s, K, flags);
+    const Switches sw = read_switches();
+    const bool rp = use_rp(sw, s);
+    const int rpp = rp ? rp_paired(sw, K) : 0;
+    int wh = 0, ww = 0, lds = lds_need(sw, rp, rpp, s + 1, s + 1, s, K, flags);
     bool clipped = false;
     if (window_dims(c2fg, r2fg, border, s, ctx->cur[1].rows, ctx->cur[1].cols, wh, ww, &clipped))
-        lds = lds_need(rp, rpp, wh, ww, s, K, flags);
+        lds = lds_need(sw, rp, rpp, wh, ww, s, K, flags);
     // (the one-point kernels do not take windows clipped by the edge of image 2: the batch entry points run them through the
     // large-window pipeline - classify_points)
     if (clipped) return fail(SID_PM_ERR_UNSUPPORTED, "debug_point: the search window is clipped by the edge of image 2 (%dx%d); "
@@ -1427,7 +1024,7 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
     std::vector<uint16_t> sampv;
     int nflag = 0;
     // (rot_order = 1: no offset table - every template sample is interpolated in float64 by the general sampler)
-    if (!getenv("SID_PM_NO_SAMP_TABLE") && ((flags >> 3) & 7u) == 0u) nflag = make_samp(rotv, K, s, sampv);
+    if (!sw.no_samp_table && ((flags >> 3) & 7u) == 0u) nflag = make_samp(rotv, K, s, sampv);
     DevBuf<float> dccm, dhes;
     DevBuf<uint8_t> dpre;                                              // rot_order 2..5: this point's templates, sampled from the spline coefficients
     DevBuf<long long> dcyc;
@@ -1441,7 +1038,7 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
         (rc = dout.reserve(5)) || (rc = dord.reserve(1)) || (rc = dij.reserve(3)) || (rc = dshape.reserve(2)) ||
         (rc = dt.reserve(tcount)) || (rc = dccm.reserve((size_t)std::max<int64_t>(cap, 1))) ||
         (rc = dhes.reserve((size_t)std::max<int64_t>(cap, 1))) || (rc = dcyc.reserve(32)) ||
-        (rc = dsamp.reserve(sampv.size() + 4)) || (rc = dgs.reserve(64 + (size_t)(wh > s ? sid::rp_block_entries(wh - s + 1, ww - s + 1, rp_rows(rpp, 4), 16 >> rpp, false, keep_acc_policy(rp, rpp, K)) : 64))) || (rc = drec.reserve(1))) { cleanup(); return rc; }
+        (rc = dsamp.reserve(sampv.size() + 4)) || (rc = dgs.reserve(64 + (size_t)(wh > s ? sid::rp_block_entries(wh - s + 1, ww - s + 1, rp_rows(rpp, 4), 16 >> rpp, false, keep_acc_policy(sw, rp, rpp, K)) : 64))) || (rc = drec.reserve(1))) { cleanup(); return rc; }
     const double v5[5] = {c1, r1, c2fg, r2fg, border};
     const int32_t zero = 0, shape0[2] = {0, 0};
     hipError_t e = hipSuccess;
@@ -1483,9 +1080,9 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
             A.pre = dpre.p;
         }
         A.gsii = dgs.p + 64; A.gsii_off = dgs.p; A.rec = drec.p;
-        A.gs_keep_acc = keep_acc_policy(rp, rpp, K) ? 1u : 0u;
+        A.gs_keep_acc = keep_acc_policy(sw, rp, rpp, K) ? 1u : 0u;
         step((hipError_t)(rp ? sid::launch_pm_rp(A, lds, 256, 4, rpp, 0, 3, ctx->stream)
-                                       : sid::launch_pm_mfma(A, lds, 256, 4, use_paired(K), ctx->stream)));
+                                       : sid::launch_pm_mfma(A, lds, 256, 4, use_paired(sw, K), ctx->stream)));
         step(hipStreamSynchronize(ctx->stream));
         if (templates) step(hipMemcpy(templates, dt.p, tcount, hipMemcpyDeviceToHost));
         if (ccm && cap > 0) step(hipMemcpy(ccm, dccm.p, sizeof(float) * cap, hipMemcpyDeviceToHost));
@@ -1557,98 +1154,19 @@ SID_EXPORT int sid_pm_debug_hypot_selftest(sid_pm_ctx *ctx, uint64_t seed, int64
     return SID_PM_OK;
 }
 
-// Estimated cost of a grid point in nanoseconds of one MI355X, for cutting a set of points into shards of equal cost
-// (sea_ice_drift_amd/dist.py).  Not a table per border: the cost follows what the kernel executes for the point - the
-// matrix instructions of the sweep (bands x placement tiles x template row pairs, per group of angles), those of the
-// winner's NCC matrix, the placements themselves - times a factor for the residency class of its LDS footprint (fewer
-// co-resident workgroups hide less latency).  The six constants were fitted to tools/border_cost.py (template side 34, 15
-// angles, borders 20..50: within 4 % everywhere); what matters to the sharding are the ratios between points.
-static int estimate_points(const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, double *cost_ns, int32_t *per_cu_out)
+// the cost model of pm_plan.h (estimate_points) behind the argument checks of the ABI, with the switches of this call
+static int estimate_checked(const Switches &sw, const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, double *cost_ns, int32_t *per_cu_out)
 {
     if (n < 0 || (n > 0 && (!border || (!cost_ns && !per_cu_out)))) return fail(SID_PM_ERR_ARG, "bad argument");
-    const int s = img_size, K = n_angles;
-    if (s < 2 || s > sid::kLargeMaxSide || K < 1) return fail(SID_PM_ERR_UNSUPPORTED, "img_size / angle count not supported");
-    const bool small_ok = sid::mfma_img_size_supported(s);
-    // a point of the large-window pipeline (pm_large.hip: batches of up to 64 points, each tiled over the device): the matrix
-    // instructions of lw_corr and the per-placement passes, fitted to profiles/r06_large_window_bench_batched.jsonl (11 / 19 / 46 us
-    // at borders 112 / 160 / 250 with 15 angles, 9 us at 100 px, 6 us at 65 px: within 40 %); the ~25 launches of a batch
-    // (0.15 ms) are priced per batch by sid_pm_estimate_run_time
-    auto large_cost = [&](int wn) {
-        const double r = (double)(wn - s + 1);
-        const double tiles = ceil(r / 64.0) * ceil(r / 16.0) * (double)((K + 15) / 16);
-        return 3000.0 + 4.5 * tiles * (double)(s + 3) * (double)((s + 63) / 64);
-    };
-    const bool rp = use_rp(s, K);
-    const int rpp = rp ? rp_paired(K) : 0;
-    const int hws = (int)((double)s / 2.0);
-    const int groups = (K + sid::kRpGroup - 1) / sid::kRpGroup;
-    // round 4 (transposed strip columns, sum w'^2 in global memory where it lifts the residency class): refitted to
-    // tools/border_cost.py on the shipped library, one set per kernel family - full table / two / four slot groups - within
-    // 2.3 / 4.3 / 7 % of the measured staircase (profiles/r04_border_cost.json)
-    struct Fit { double sweep, winner, pos, fixed, two, one, gs, four; };
-    static const Fit kFit[3] = {{3.4646e-3, 2.2848e-2, 7.6082e-3, 29.955, 1.1228, 1.2800, 1.06500, 0.88700},
-                                {3.9853e-3, 1.7996e-2, 7.6297e-3, 25.686, 1.2348, 1.3287, 0.99236, 0.91000},
-                                {2.5923e-3, 1.8513e-2, 6.4734e-3, 24.173, 1.2518, 1.3574, 1.00890, 0.86000}};   // (last column: the three-wavefront class, refitted to tools/archive/r4_w3.sh / r4_w3p.sh)
-    const Fit &F = kFit[rpp];
-    constexpr double kBigFactor = 1.25;   // every per-placement table through L2 / HBM (measured at borders 70 .. 100: tools/border_cost.py)
-    const double kSweep = F.sweep, kWinner = F.winner, kPos = F.pos, kFixed = F.fixed, kTwoPerCu = F.two, kOnePerCu = F.one, kFourPerCu = F.four;
-    for (int64_t i = 0; i < n; ++i) {
-        const double b = border[i];
-        if (per_cu_out) per_cu_out[i] = kMaxPerCu;
-        if (!(b >= 0.0 && b < 4096.0)) { if (cost_ns) cost_ns[i] = kFixed; continue; }      // NaN / absurd: a point that writes NaN at once
-        const int wn = 2 * hws + 2 * (int)b + 1, r = wn - s + 1;
-        if (r < 2) { if (cost_ns) cost_ns[i] = kFixed; continue; }
-        double sweep, winner, cls_factor;
-        int cls = kMaxPerCu;
-        if (!small_ok) {
-            if (cost_ns) cost_ns[i] = large_cost(wn);
-            if (per_cu_out) per_cu_out[i] = 1 + SID_PM_CLASS_LARGE;
-            continue;
-        }
-        if (rp) {
-            static const bool no_band8 = getenv("SID_PM_NO_BAND8") != nullptr;
-            const ShapeClass sc = shape_class(rp, rpp, wn, wn, s, K, flags, sid::mfma_band8_supported(s) && !no_band8 && !rpp, false);   // (the flags decide the Hessian's LDS: rp_own_hes)
-            if (sc.lds > sid::max_lds_bytes()) {                               // beyond the LDS of one workgroup: the large-window pipeline
-                if (cost_ns) cost_ns[i] = large_cost(wn);
-                if (per_cu_out) per_cu_out[i] = 1 + SID_PM_CLASS_LARGE;
-                continue;
-            }
-            const sid::RpLdsLayout L4 = sid::rp_lds_layout(wn, wn, s, K <= sid::kRpGroup, rp_rows(rpp, 4), 0, sid::rp_tab_pitch(rpp), rp_own_hes(K, flags), sc.gs);
-            const int per_cu = std::max(1, sc.cls), band = sc.band;            // (big layouts - class 0 - run one workgroup per CU, full table)
-            const int rows = sc.big ? 4 : rp_rows(rpp, band), tiles = 2 * L4.npair + L4.nsingle;
-            const double per_row_tile = (double)((s + 1) / 2 + s / 2 + 1) / 2.0 + (double)(((s - 32 + 1) / 2) * 2);
-            // work items are dealt to the wavefronts of the workgroup: the busiest wavefront sets the pace
-            const int nwaves = per_cu == 1 ? 12 : 4;
-            // (the sweep's items: rp_sweep_items - ragged single items where the full-table kernels pack the leftover columns of all bands)
-            const int sw_units = sid::rp_sweep_items(r, r, rows, sid::rp_sweep_ragged_ok(sc.big ? 0 : rpp)).units;
-            const int units = ((sw_units + nwaves - 1) / nwaves) * nwaves, wunits = ((((r + 15) / 16) * tiles + nwaves - 1) / nwaves) * nwaves;
-            sweep = groups * (sc.big ? 1.0 : rpp == 2 ? 0.33 : rpp == 1 ? 0.55 : 1.0) * units * (rows * per_row_tile + 2.0);
-            winner = wunits * 76.0;
-            cls_factor = ((per_cu >= 4 && max_per_cu(rp, rpp) == 4) ? kFourPerCu : per_cu >= 3 ? 1.0 : per_cu == 2 ? kTwoPerCu : kOnePerCu) * (sc.gs ? F.gs : 1.0) * (sc.big ? kBigFactor : 1.0);
-            cls = std::max(1, std::min(per_cu, max_per_cu(rp, rpp))) + (sc.gs ? 16 : 0) + (sc.big ? 32 : 0) + (sc.w3_pitch > 1104 ? 64 : 0);   // (+ 64: the second launch of the three-wavefront class)   // (+ 16: the launches that keep sum w'^2 in global memory are launches of their own)
-        } else {
-            const sid::MfmaLdsLayout L = sid::mfma_lds_layout(wn, wn, s, 4, use_paired(K));
-            if (L.total > sid::max_lds_bytes()) {
-                if (cost_ns) cost_ns[i] = large_cost(wn);
-                if (per_cu_out) per_cu_out[i] = 1 + SID_PM_CLASS_LARGE;
-                continue;
-            }
-            const int per_cu = blocks_per_cu(L.total), ntx = (r + 15) / 16;
-            sweep = groups * (double)r * ntx * s * (use_paired(K) ? 0.55 : 1.0) * 1.3;    // one template row per MFMA
-            winner = (double)((r + 15) / 16) * ntx * (16 + s - 1) * 2.0;
-            cls_factor = per_cu >= 3 ? 1.0 : per_cu == 2 ? kTwoPerCu : kOnePerCu;
-            cls = std::max(1, std::min(per_cu, kMaxPerCu));
-        }
-        if (cost_ns) cost_ns[i] = (kSweep * sweep + kWinner * winner + kPos * (double)r * r + kFixed) * cls_factor;
-        if (per_cu_out) per_cu_out[i] = cls;
-    }
+    if (img_size < 2 || img_size > sid::kLargeMaxSide || n_angles < 1) return fail(SID_PM_ERR_UNSUPPORTED, "img_size / angle count not supported");
+    sid::plan::estimate_points(sw, border, n, img_size, n_angles, flags, cost_ns, per_cu_out);
     return SID_PM_OK;
 }
 
 SID_EXPORT int sid_pm_estimate_cost(const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, double *cost_ns)
 {
     if (n > 0 && !cost_ns) return fail(SID_PM_ERR_ARG, "bad argument");
-    return estimate_points(border, n, img_size, n_angles, flags, cost_ns, nullptr);
+    return estimate_checked(read_switches(), border, n, img_size, n_angles, flags, cost_ns, nullptr);
 }
 
 // Launch class of a point of that border (include/sid_pm.h): workgroups per CU in the low four bits - a launch runs 256 x that
@@ -1657,7 +1175,7 @@ SID_EXPORT int sid_pm_estimate_cost(const double *border, int64_t n, int img_siz
 SID_EXPORT int sid_pm_estimate_residency(const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, int32_t *per_cu)
 {
     if (n > 0 && !per_cu) return fail(SID_PM_ERR_ARG, "bad argument");
-    return estimate_points(border, n, img_size, n_angles, flags, nullptr, per_cu);
+    return estimate_checked(read_switches(), border, n, img_size, n_angles, flags, nullptr, per_cu);
 }
 
 // Estimated kernel time of ONE run over these points (nanoseconds): per launch class the sum of the point costs plus the tail of
@@ -1673,13 +1191,13 @@ SID_EXPORT int sid_pm_estimate_run_time(const double *border, int64_t n, int img
     if (n == 0) return SID_PM_OK;
     std::vector<double> cost((size_t)n);
     std::vector<int32_t> cls((size_t)n);
-    if (int rc = estimate_points(border, n, img_size, n_angles, flags, cost.data(), cls.data())) return rc;
+    const Switches sw = read_switches();
+    if (int rc = estimate_checked(sw, border, n, img_size, n_angles, flags, cost.data(), cls.data())) return rc;
     struct Part { double sum = 0, count = 0; };
     Part parts[256];
     for (int64_t i = 0; i < n; ++i) { Part &p = parts[cls[(size_t)i] & 255]; p.sum += cost[(size_t)i]; p.count += 1; }
     static const double kTail[5] = {0.5, 1.0, 0.7, 0.5, 0.5};
-    const char *be = getenv("SID_DIST_TAIL_BLEND");
-    const double blend = be ? atof(be) : 0.7;
+    const double blend = sw.tail_blend;
     double large = 0, sum_all = 0, rounds = 0, tail_max = 0, tail_sum = 0, lat_max = 0, seq = 0;
     size_t nparts = 0;
     for (int c = 0; c < 256; ++c) {
@@ -1693,7 +1211,7 @@ SID_EXPORT int sid_pm_estimate_run_time(const double *border, int64_t n, int img
         seq += std::max(p.sum + tail, latency);
     }
     double t = seq;
-    if (side_by_side_rule(nparts, rounds)) t = std::max(sum_all + tail_max + blend * (tail_sum - tail_max), lat_max);
+    if (side_by_side_rule(sw, nparts, rounds)) t = std::max(sum_all + tail_max + blend * (tail_sum - tail_max), lat_max);
     *time_ns = t + large;
     return SID_PM_OK;
 }
