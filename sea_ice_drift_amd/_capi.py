@@ -49,6 +49,7 @@ DEFOR_SYMBOLS = ('sid_defor_triangulation', 'sid_defor_elems', 'sid_defor_triang
 DEFOR_ERR_INDEX = -32   # include/sid_defor.h SID_DEFOR_ERR_INDEX
 # every symbol include/sid_grid.h declares (outlier filter and deformation on a grid of drift vectors, same library)
 GRID_SYMBOLS = ('sid_grid_filter', 'sid_grid_deformation', 'sid_grid_filter_device', 'sid_grid_deformation_device',
+                'sid_grid_fill', 'sid_grid_smooth', 'sid_grid_fill_device', 'sid_grid_smooth_device',
                 'sid_grid_last_error', 'sid_grid_release')
 GRID_DIAGONALS = {'shorter': 0, 'main': 1, 'anti': 2}     # SID_GRID_DIAG_*
 GRID_TILE = (8, 32)                                       # SID_GRID_TILE_ROWS, SID_GRID_TILE_COLS: the filter kernel's tile
@@ -190,6 +191,12 @@ def lib():
         L.sid_grid_deformation_device.argtypes = [vp] * 5 + [C.c_int64, C.c_int64, C.c_int] + [vp] * 7
         L.sid_grid_last_error.restype = C.c_char_p
         L.sid_grid_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_grid_fill'):              # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        vp, i64 = C.c_void_p, C.c_int64
+        L.sid_grid_fill.argtypes = [C.c_int, _f64p, _f64p, _u8p, _u8p, i64, i64, C.c_int, C.c_int, C.c_int, _f64p, _f64p, _i32p]
+        L.sid_grid_fill_device.argtypes = [vp] * 4 + [i64, i64, C.c_int, C.c_int, C.c_int] + [vp] * 4
+        L.sid_grid_smooth.argtypes = [C.c_int, _f64p, _f64p, _u8p, i64, i64, _f64p, C.c_int, _f64p, _f64p]
+        L.sid_grid_smooth_device.argtypes = [vp] * 3 + [i64, i64, _f64p, C.c_int] + [vp] * 3
     if hasattr(L, 'sid_warp_image'):
         vp = C.c_void_p
         tail = [C.c_int64, C.c_int64, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double,
@@ -884,6 +891,41 @@ def grid_deformation_device(x, y, u, v, valid, rows, cols, diagonal, outs, strea
     """``sid_grid_deformation_device`` on raw device pointers: outs = (e1, e2, e3, a, p, t)."""
     _grid_check(lib().sid_grid_deformation_device(*[_vp(q) for q in (x, y, u, v, valid)], int(rows), int(cols),
                                                   int(diagonal), *[_vp(q) for q in outs], _vp(stream)))
+
+
+def grid_fill(u, v, valid, domain, radius, min_neighbours, max_passes, device=0):
+    """``sid_grid_fill`` on host arrays: u, v float64 [rows, cols], valid and domain uint8 [rows, cols] or None (C-contiguous)
+    -> u_out, v_out float64 [rows, cols], gen int32 [rows, cols].  device=-1: the kernels' source in a host loop (tests)."""
+    rows, cols = u.shape
+    uo, vo = np.empty((rows, cols), dtype=np.float64), np.empty((rows, cols), dtype=np.float64)
+    gen = np.empty((rows, cols), dtype=np.int32)
+    _grid_check(lib().sid_grid_fill(int(device), _p(u, _f64p), _p(v, _f64p), _opt_u8(valid), _opt_u8(domain), rows, cols,
+                                    int(radius), int(min_neighbours), int(max_passes), _p(uo, _f64p), _p(vo, _f64p),
+                                    _p(gen, _i32p)))
+    return uo, vo, gen
+
+
+def grid_fill_device(u, v, valid, domain, rows, cols, radius, min_neighbours, max_passes, u_out, v_out, gen, stream):
+    """``sid_grid_fill_device`` on raw device pointers (torch ``data_ptr()``; valid, domain 0 for none)."""
+    _grid_check(lib().sid_grid_fill_device(*[_vp(q) for q in (u, v, valid, domain)], int(rows), int(cols), int(radius),
+                                           int(min_neighbours), int(max_passes), _vp(u_out), _vp(v_out), _vp(gen),
+                                           _vp(stream)))
+
+
+def grid_smooth(u, v, valid, weights, radius, device=0):
+    """``sid_grid_smooth`` on host arrays: u, v float64 [rows, cols], valid uint8 or None, weights float64
+    [2 radius + 1, 2 radius + 1] (C-contiguous all) -> u_out, v_out float64 [rows, cols].  device=-1: the host loop (tests)."""
+    rows, cols = u.shape
+    uo, vo = np.empty((rows, cols), dtype=np.float64), np.empty((rows, cols), dtype=np.float64)
+    _grid_check(lib().sid_grid_smooth(int(device), _p(u, _f64p), _p(v, _f64p), _opt_u8(valid), rows, cols, _p(weights, _f64p),
+                                      int(radius), _p(uo, _f64p), _p(vo, _f64p)))
+    return uo, vo
+
+
+def grid_smooth_device(u, v, valid, rows, cols, weights, radius, u_out, v_out, stream):
+    """``sid_grid_smooth_device`` on raw device pointers; `weights` is a host float64 array (it travels as a kernel argument)."""
+    _grid_check(lib().sid_grid_smooth_device(*[_vp(q) for q in (u, v, valid)], int(rows), int(cols), _p(weights, _f64p),
+                                             int(radius), _vp(u_out), _vp(v_out), _vp(stream)))
 
 
 def warp_image(x, y, xs, ys, valid, src, dtype, src_shape, out_shape, order, fill, diagonal, flags, want_out, want_covered,

@@ -6,6 +6,9 @@
 //                  neighbours read from there: no per-thread array.
 //   k_grid_defor   one thread per cell: the four ring nodes of x, y, u, v, the triangle rule, two slots written
 //                  structure-of-arrays.
+//   k_grid_fill    (section 23) one launch per pass of the gap filling, the filter's tiles; pass 1 from the inputs, later passes
+//                  in place on the outputs, told apart by each node's generation.
+//   k_grid_smooth  (section 23) normalised convolution on the same tiles, the weight table a kernel argument.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -94,6 +97,150 @@ void host_filter(const double *u, const double *v, const uint8_t *valid, int64_t
         }
 }
 
+// ---------------------------------------------------------------- gap filling
+// The neighbours of one pass from the arrays themselves, for the host instance: a generation in 0..pass-1 and finite values
+struct HostFillGet {
+    const double *uo, *vo;
+    const int32_t *gen;
+    int64_t rows, cols, r, c;
+    int pass;
+    void operator()(int di, int dj, double &a, double &b) const
+    {
+        const int64_t rr = r + di, cc = c + dj;
+        a = NAN; b = NAN;
+        if (rr < 0 || rr >= rows || cc < 0 || cc >= cols) return;
+        const int64_t k = rr * cols + cc;
+        if (gen[k] >= 0 && gen[k] < pass && isfinite(uo[k]) && isfinite(vo[k])) { a = uo[k]; b = vo[k]; }
+    }
+};
+
+// One pass.  Pass 1 reads the inputs (its neighbours are generation 0: the usable nodes) and writes every output element.
+// Passes 2 and up work in place on the outputs: a node is staged as a neighbour only with a generation in 0..pass-1, so one
+// that another workgroup fills during this launch reads as "no generation" or as `pass` and is left out either way - no
+// ordering between threads and no second buffer.  A workgroup without a candidate stages nothing.
+__global__ __launch_bounds__(kBlock) void k_grid_fill(const double *__restrict__ u, const double *__restrict__ v,
+                                                      const uint8_t *__restrict__ valid, const uint8_t *__restrict__ domain,
+                                                      int64_t rows, int64_t cols, int64_t tiles_c, int radius, int min_neighbours,
+                                                      int pass, double *uo, double *vo, int32_t *gen)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int hh = kTR + 2 * radius, hw = kTC + 2 * radius;
+    double *su = reinterpret_cast<double *>(smem), *sv = su + hh * hw;
+    const int64_t tile = blockIdx.x, tr = tile / tiles_c, tc = tile - tr * tiles_c;
+    const int ti = threadIdx.x / kTC, tj = threadIdx.x - ti * kTC;
+    const int64_t r = tr * kTR + ti, c = tc * kTC + tj, k = r * cols + c;
+    const bool inside = r < rows && c < cols;
+    double fu = NAN, fv = NAN;                                     // what pass 1 writes for a node that stays unfilled
+    int32_t g = -1;
+    bool candidate = false;
+    if (inside) {
+        const bool open = !domain || domain[k] != 0;
+        if (pass == 1) {
+            const double uu = u[k], vv = v[k];
+            if (sid_grid::usable_uv(valid, k, uu, vv)) { fu = uu; fv = vv; g = 0; }
+            candidate = g < 0 && open;
+        } else {
+            candidate = gen[k] < 0 && open;
+        }
+    }
+    if (!__syncthreads_or(candidate)) {                            // (the same answer in every thread of the workgroup)
+        if (pass == 1 && inside) { uo[k] = fu; vo[k] = fv; gen[k] = g; }
+        return;
+    }
+    const int64_t r0 = tr * kTR - radius, c0 = tc * kTC - radius;
+    for (int e = threadIdx.x; e < hh * hw; e += kBlock) {
+        const int li = e / hw, lj = e - li * hw;
+        const int64_t rr = r0 + li, cc = c0 + lj;
+        double a = NAN, b = NAN;
+        if (rr >= 0 && rr < rows && cc >= 0 && cc < cols) {
+            const int64_t q = rr * cols + cc;
+            if (pass == 1) {
+                const double uu = u[q], vv = v[q];
+                if (sid_grid::usable_uv(valid, q, uu, vv)) { a = uu; b = vv; }
+            } else {
+                const int32_t gq = gen[q];
+                if (gq >= 0 && gq < pass) {
+                    const double uu = uo[q], vv = vo[q];
+                    if (isfinite(uu) && isfinite(vv)) { a = uu; b = vv; }
+                }
+            }
+        }
+        su[e] = a; sv[e] = b;
+    }
+    __syncthreads();
+    if (!inside) return;
+    if (candidate) {
+        const LdsGet get = {su, sv, hw, ti + radius, tj + radius};
+        if (sid_grid::fill_node(get, radius, min_neighbours, fu, fv)) g = pass;
+    }
+    if (pass == 1 || g == pass) { uo[k] = fu; vo[k] = fv; gen[k] = g; }
+}
+
+void host_fill(const double *u, const double *v, const uint8_t *valid, const uint8_t *domain, int64_t rows, int64_t cols,
+               int radius, int min_neighbours, int max_passes, double *uo, double *vo, int32_t *gen)
+{
+    for (int64_t k = 0; k < rows * cols; ++k) {
+        const bool ok = sid_grid::usable_uv(valid, k, u[k], v[k]);
+        uo[k] = ok ? u[k] : NAN; vo[k] = ok ? v[k] : NAN; gen[k] = ok ? 0 : -1;
+    }
+    for (int pass = 1; pass <= max_passes; ++pass) {               // a node filled in this pass has gen = pass: not a neighbour
+        bool filled = false;
+        for (int64_t r = 0; r < rows; ++r)
+            for (int64_t c = 0; c < cols; ++c) {
+                const int64_t k = r * cols + c;
+                if (gen[k] >= 0 || (domain && domain[k] == 0)) continue;
+                const HostFillGet get = {uo, vo, gen, rows, cols, r, c, pass};
+                double fu, fv;
+                if (sid_grid::fill_node(get, radius, min_neighbours, fu, fv)) { uo[k] = fu; vo[k] = fv; gen[k] = pass; filled = true; }
+            }
+        if (!filled) break;
+    }
+}
+
+// ---------------------------------------------------------------- smoothing
+// (LdsGet and HostGet at (0, 0) give the node itself: the centre takes part)
+__global__ __launch_bounds__(kBlock) void k_grid_smooth(const double *__restrict__ u, const double *__restrict__ v,
+                                                        const uint8_t *__restrict__ valid, int64_t rows, int64_t cols,
+                                                        int64_t tiles_c, sid_grid::Weights wt, int radius,
+                                                        double *__restrict__ uo, double *__restrict__ vo)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int hh = kTR + 2 * radius, hw = kTC + 2 * radius;
+    double *su = reinterpret_cast<double *>(smem), *sv = su + hh * hw;
+    const int64_t tile = blockIdx.x, tr = tile / tiles_c, tc = tile - tr * tiles_c;
+    const int64_t r0 = tr * kTR - radius, c0 = tc * kTC - radius;
+    for (int e = threadIdx.x; e < hh * hw; e += kBlock) {
+        const int li = e / hw, lj = e - li * hw;
+        const int64_t r = r0 + li, c = c0 + lj;
+        double a = NAN, b = NAN;
+        if (r >= 0 && r < rows && c >= 0 && c < cols) {
+            const int64_t k = r * cols + c;
+            const double uu = u[k], vv = v[k];
+            if (sid_grid::usable_uv(valid, k, uu, vv)) { a = uu; b = vv; }
+        }
+        su[e] = a; sv[e] = b;
+    }
+    __syncthreads();
+    const int ti = threadIdx.x / kTC, tj = threadIdx.x - ti * kTC;
+    const int64_t r = tr * kTR + ti, c = tc * kTC + tj;
+    if (r >= rows || c >= cols) return;
+    const LdsGet get = {su, sv, hw, ti + radius, tj + radius};
+    double us, vs;
+    sid_grid::smooth_node(get, radius, wt, us, vs);
+    uo[r * cols + c] = us;
+    vo[r * cols + c] = vs;
+}
+
+void host_smooth(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols, const sid_grid::Weights &wt,
+                 int radius, double *uo, double *vo)
+{
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t c = 0; c < cols; ++c) {
+            const HostGet get = {u, v, valid, rows, cols, r, c};
+            sid_grid::smooth_node(get, radius, wt, uo[r * cols + c], vo[r * cols + c]);
+        }
+}
+
 // ---------------------------------------------------------------- deformation
 // Cell k = i (cols - 1) + j of either instance: gather the ring, apply the rule, write both slots
 __host__ __device__ inline void one_cell(const double *x, const double *y, const double *u, const double *v, const uint8_t *valid,
@@ -163,7 +310,81 @@ int check_defor_args(const void *x, const void *y, const void *u, const void *v,
     return SID_PM_OK;
 }
 
+// [a, a + na) and [b, b + nb) bytes share a byte (never for an empty range)
+bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return na && nb && pa < pb + nb && pb < pa + na;
+}
+
+// two float64 inputs and two float64 outputs of rows * cols elements each: no output on an input or on the other output
+int check_no_alias(const double *u, const double *v, int64_t rows, int64_t cols, const double *uo, const double *vo)
+{
+    const size_t nb = sizeof(double) * (size_t)(rows * cols);
+    if (overlap(uo, nb, u, nb) || overlap(uo, nb, v, nb) || overlap(vo, nb, u, nb) || overlap(vo, nb, v, nb) || overlap(uo, nb, vo, nb))
+        return fail(SID_PM_ERR_ARG, "u_out and v_out may not overlap u, v or each other");
+    return SID_PM_OK;
+}
+
+int check_fill_args(const double *u, const double *v, int64_t rows, int64_t cols, int radius, int min_neighbours, int max_passes,
+                    const double *uo, const double *vo, const int32_t *gen)
+{
+    if (radius < 1 || radius > 2) return fail(SID_PM_ERR_ARG, "radius must be 1 or 2 (got %d)", radius);
+    if (min_neighbours < 1 || min_neighbours > (2 * radius + 1) * (2 * radius + 1) - 1)
+        return fail(SID_PM_ERR_ARG, "min_neighbours must be in 1..%d (got %d)", (2 * radius + 1) * (2 * radius + 1) - 1, min_neighbours);
+    if (max_passes < 1 || max_passes > 256) return fail(SID_PM_ERR_ARG, "max_passes must be in 1..256 (got %d)", max_passes);
+    if (int rc = check_size(rows, cols)) return rc;
+    if (!u || !v || !uo || !vo || !gen) return fail(SID_PM_ERR_ARG, "null pointer");
+    const size_t nb = sizeof(double) * (size_t)(rows * cols), ng = sizeof(int32_t) * (size_t)(rows * cols);
+    if (overlap(gen, ng, u, nb) || overlap(gen, ng, v, nb) || overlap(gen, ng, uo, nb) || overlap(gen, ng, vo, nb))
+        return fail(SID_PM_ERR_ARG, "gen may not overlap u, v, u_out or v_out");
+    return check_no_alias(u, v, rows, cols, uo, vo);
+}
+
+// The checked copy of the caller's table
+int check_smooth_args(const double *u, const double *v, int64_t rows, int64_t cols, const double *weights, int radius,
+                      const double *uo, const double *vo, sid_grid::Weights &wt)
+{
+    if (radius < 1 || radius > 2) return fail(SID_PM_ERR_ARG, "radius must be 1 or 2 (got %d)", radius);
+    if (!weights) return fail(SID_PM_ERR_ARG, "null pointer");
+    const int side = 2 * radius + 1;
+    wt = sid_grid::Weights();
+    for (int i = 0; i < side * side; ++i) {
+        if (!isfinite(weights[i]) || weights[i] < 0.0)
+            return fail(SID_PM_ERR_ARG, "weights[%d][%d] must be finite and >= 0 (got %g)", i / side, i % side, weights[i]);
+        wt.w[i] = weights[i];
+    }
+    if (!(weights[radius * side + radius] > 0.0)) return fail(SID_PM_ERR_ARG, "the centre weight must be > 0");
+    if (int rc = check_size(rows, cols)) return rc;
+    if (!u || !v || !uo || !vo) return fail(SID_PM_ERR_ARG, "null pointer");
+    return check_no_alias(u, v, rows, cols, uo, vo);
+}
+
 // ---------------------------------------------------------------- launches
+// One launch per pass, all of them: nothing returns to the host that could end the series early, and a pass without a
+// candidate costs each workgroup one read of its nodes' generations.
+int launch_fill(const double *u, const double *v, const uint8_t *valid, const uint8_t *domain, int64_t rows, int64_t cols,
+                int radius, int min_neighbours, int max_passes, double *uo, double *vo, int32_t *gen, hipStream_t st)
+{
+    const int64_t tiles_r = (rows + kTR - 1) / kTR, tiles_c = (cols + kTC - 1) / kTC;
+    for (int pass = 1; pass <= max_passes; ++pass) {
+        hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(tiles_r * tiles_c)), dim3(kBlock), filter_lds_bytes(radius), st,
+                           u, v, valid, domain, rows, cols, tiles_c, radius, min_neighbours, pass, uo, vo, gen);
+        HIP_TRY(hipGetLastError());
+    }
+    return SID_PM_OK;
+}
+
+int launch_smooth(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols, const sid_grid::Weights &wt,
+                  int radius, double *uo, double *vo, hipStream_t st)
+{
+    const int64_t tiles_r = (rows + kTR - 1) / kTR, tiles_c = (cols + kTC - 1) / kTC;
+    hipLaunchKernelGGL(k_grid_smooth, dim3((unsigned)(tiles_r * tiles_c)), dim3(kBlock), filter_lds_bytes(radius), st,
+                       u, v, valid, rows, cols, tiles_c, wt, radius, uo, vo);
+    HIP_TRY(hipGetLastError());
+    return SID_PM_OK;
+}
+
 int launch_filter(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols, double eps, double threshold,
                   int radius, int min_neighbours, uint8_t *keep, double *res, hipStream_t st)
 {
@@ -210,6 +431,91 @@ SID_EXPORT int sid_grid_deformation_device(const double *x, const double *y, con
     if (int rc = check_defor_args(x, y, u, v, rows, cols, diagonal, e1, e2, e3, a, p, t)) return rc;
     if (rows < 2 || cols < 2) return SID_PM_OK;
     return launch_defor(x, y, u, v, valid, rows, cols, diagonal, e1, e2, e3, a, p, t, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+SID_EXPORT int sid_grid_fill_device(const double *u, const double *v, const uint8_t *valid, const uint8_t *domain, int64_t rows,
+                                    int64_t cols, int radius, int min_neighbours, int max_passes, double *u_out, double *v_out,
+                                    int32_t *gen, void *hip_stream)
+{
+    if (int rc = check_fill_args(u, v, rows, cols, radius, min_neighbours, max_passes, u_out, v_out, gen)) return rc;
+    if (rows * cols == 0) return SID_PM_OK;
+    return launch_fill(u, v, valid, domain, rows, cols, radius, min_neighbours, max_passes, u_out, v_out, gen,
+                       reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+SID_EXPORT int sid_grid_smooth_device(const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,
+                                      const double *weights, int radius, double *u_out, double *v_out, void *hip_stream)
+{
+    sid_grid::Weights wt;
+    if (int rc = check_smooth_args(u, v, rows, cols, weights, radius, u_out, v_out, wt)) return rc;
+    if (rows * cols == 0) return SID_PM_OK;
+    return launch_smooth(u, v, valid, rows, cols, wt, radius, u_out, v_out, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+SID_EXPORT int sid_grid_fill(int device, const double *u, const double *v, const uint8_t *valid, const uint8_t *domain,
+                             int64_t rows, int64_t cols, int radius, int min_neighbours, int max_passes,
+                             double *u_out, double *v_out, int32_t *gen)
+{
+    if (int rc = check_fill_args(u, v, rows, cols, radius, min_neighbours, max_passes, u_out, v_out, gen)) return rc;
+    if (rows * cols == 0) return SID_PM_OK;
+    if (device == -1) {
+        host_fill(u, v, valid, domain, rows, cols, radius, min_neighbours, max_passes, u_out, v_out, gen);
+        return SID_PM_OK;
+    }
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n;
+    double *du, *dv, *duo, *dvo;
+    int32_t *dgen;
+    uint8_t *dvalid, *ddomain;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            du = c.take<double>(n); dv = c.take<double>(n); duo = c.take<double>(n); dvo = c.take<double>(n);
+            dgen = c.take<int32_t>(n);
+            dvalid = c.take<uint8_t>(n, valid != nullptr); ddomain = c.take<uint8_t>(n, domain != nullptr);
+        }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(dv, v, nb, hipMemcpyHostToDevice, 0));
+    if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
+    if (domain) HIP_TRY(hipMemcpyAsync(ddomain, domain, n, hipMemcpyHostToDevice, 0));
+    if (int rc = launch_fill(du, dv, dvalid, ddomain, rows, cols, radius, min_neighbours, max_passes, duo, dvo, dgen, 0)) return rc;
+    HIP_TRY(hipMemcpyAsync(u_out, duo, nb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpyAsync(v_out, dvo, nb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpyAsync(gen, dgen, sizeof(int32_t) * n, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
+}
+
+SID_EXPORT int sid_grid_smooth(int device, const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,
+                               const double *weights, int radius, double *u_out, double *v_out)
+{
+    sid_grid::Weights wt;
+    if (int rc = check_smooth_args(u, v, rows, cols, weights, radius, u_out, v_out, wt)) return rc;
+    if (rows * cols == 0) return SID_PM_OK;
+    if (device == -1) {
+        host_smooth(u, v, valid, rows, cols, wt, radius, u_out, v_out);
+        return SID_PM_OK;
+    }
+    Staging s;
+    if (!s.enter(g_pool, device)) return fail(SID_PM_ERR_NODEVICE, "no such HIP device");
+    const size_t n = (size_t)(rows * cols), nb = sizeof(double) * n;
+    double *du, *dv, *duo, *dvo;
+    uint8_t *dvalid;
+    if (int rc = g_pool.carve(device, [&](Carver &c) {
+            du = c.take<double>(n); dv = c.take<double>(n); duo = c.take<double>(n); dvo = c.take<double>(n);
+            dvalid = c.take<uint8_t>(n, valid != nullptr);
+        }))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, 0));
+    HIP_TRY(hipMemcpyAsync(dv, v, nb, hipMemcpyHostToDevice, 0));
+    if (valid) HIP_TRY(hipMemcpyAsync(dvalid, valid, n, hipMemcpyHostToDevice, 0));
+    if (int rc = launch_smooth(du, dv, dvalid, rows, cols, wt, radius, duo, dvo, 0)) return rc;
+    HIP_TRY(hipMemcpyAsync(u_out, duo, nb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpyAsync(v_out, dvo, nb, hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    s.done();
+    return SID_PM_OK;
 }
 
 SID_EXPORT int sid_grid_filter(int device, const double *u, const double *v, const uint8_t *valid, int64_t rows, int64_t cols,

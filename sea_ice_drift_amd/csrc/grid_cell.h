@@ -1,6 +1,7 @@
-// grid_cell.h - the per-cell triangle rule and the per-node normalised median test of include/sid_grid.h (DESIGN.md section
-// 19), one source for the kernels of drift_grid.hip and for their host instance (device = -1).  Every float64 operation is one
-// IEEE rounding in the order of tests/grid_spec.py (-ffp-contract=off on both sides).
+// grid_cell.h - the per-cell triangle rule, the per-node normalised median test and the per-node gap
+// fill and smoothing (section 23) of include/sid_grid.h, one source for the kernels of drift_grid.hip and for their host
+// instance (device = -1).  Every float64 operation is one IEEE rounding in the order of tests/grid_spec.py and
+// tests/grid_fill_spec.py (-ffp-contract=off on both sides).
 #ifndef SID_GRID_CELL_H
 #define SID_GRID_CELL_H
 
@@ -158,6 +159,72 @@ SID_HD_INLINE void filter_node(const Get &get, int radius, double uc, double vc,
 SID_HD_INLINE bool usable_uv(const uint8_t *valid, int64_t k, double u, double v)
 {
     return (!valid || valid[k] != 0) && isfinite(u) && isfinite(v);
+}
+
+// ---------------------------------------------------------------- gap filling and smoothing
+// One candidate of one fill pass: `get` gives the neighbours that count in this pass (a generation below the pass, finite
+// values) and NaN in both for every other node.  True when the node is filled: uf, vf = the medians of the neighbours, + 0.0
+// (rank selection may pick either of two tied signed zeros; the sum is +0.0 for both).
+template <int radius, class Get>
+SID_HD_INLINE bool fill_node_r(const Get &get, int min_neighbours, double &uf, double &vf)
+{
+    int n = 0;
+#pragma unroll
+    for (int di = -radius; di <= radius; ++di)
+#pragma unroll
+        for (int dj = -radius; dj <= radius; ++dj) {
+            if (di == 0 && dj == 0) continue;
+            double a, b;
+            get(di, dj, a, b);
+            n += a == a;
+        }
+    if (n < min_neighbours) return false;                          // (min_neighbours >= 1: a median has n >= 1 values)
+    double um, vm;
+    medians<radius>(get, n, um, vm);
+    uf = um + 0.0;
+    vf = vm + 0.0;
+    return true;
+}
+
+template <class Get>
+SID_HD_INLINE bool fill_node(const Get &get, int radius, int min_neighbours, double &uf, double &vf)
+{
+    return radius == 1 ? fill_node_r<1>(get, min_neighbours, uf, vf) : fill_node_r<2>(get, min_neighbours, uf, vf);
+}
+
+// The weight table of the smoothing, row-major (2 radius + 1)^2, by value: a kernel argument, read with static indices
+struct Weights { double w[25]; };
+
+// Normalised convolution at one node: `get` gives the usable nodes, the centre at (0, 0) included, NaN in both elsewhere.
+template <int radius, class Get>
+SID_HD_INLINE void smooth_node_r(const Get &get, const Weights &wt, double &us, double &vs)
+{
+    us = NAN;
+    vs = NAN;
+    double a, b;
+    get(0, 0, a, b);
+    if (!(a == a)) return;
+    double sw = 0.0, su = 0.0, sv = 0.0;
+#pragma unroll
+    for (int di = -radius; di <= radius; ++di)
+#pragma unroll
+        for (int dj = -radius; dj <= radius; ++dj) {
+            get(di, dj, a, b);
+            if (!(a == a)) continue;
+            const double w = wt.w[(di + radius) * (2 * radius + 1) + (dj + radius)];
+            sw = sw + w;
+            su = su + w * a;
+            sv = sv + w * b;
+        }
+    us = su / sw;
+    vs = sv / sw;
+}
+
+template <class Get>
+SID_HD_INLINE void smooth_node(const Get &get, int radius, const Weights &wt, double &us, double &vs)
+{
+    if (radius == 1) smooth_node_r<1>(get, wt, us, vs);
+    else smooth_node_r<2>(get, wt, us, vs);
 }
 
 }  // namespace sid_grid
