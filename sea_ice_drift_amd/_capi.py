@@ -58,6 +58,10 @@ WARP_SYMBOLS = ('sid_warp_image', 'sid_warp_image_device', 'sid_warp_last_error'
 WARP_DTYPES = {'uint8': 0, 'float32': 1}                  # SID_WARP_U8, SID_WARP_F32
 WARP_KEEP_ZERO = 1                                        # SID_WARP_KEEP_ZERO
 WARP_TILE = (16, 64)                                      # SID_WARP_TILE_ROWS, SID_WARP_TILE_COLS: one work item of the warp kernel
+# include/sid_corr.h: local correlation of two uint8 images
+CORR_SYMBOLS = ('sid_corr_lattice', 'sid_corr_points', 'sid_corr_lattice_device', 'sid_corr_points_device', 'sid_corr_last_error',
+                'sid_corr_release')
+CORR_TILE = (8, 64)                                       # SID_CORR_TILE_ROWS, SID_CORR_TILE_COLS: the nodes of one workgroup
 
 # every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
 PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
@@ -205,6 +209,15 @@ def lib():
         L.sid_warp_image_device.argtypes = [vp] * 5 + tail + [vp]
         L.sid_warp_last_error.restype = C.c_char_p
         L.sid_warp_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_corr_lattice'):           # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        vp, i64 = C.c_void_p, C.c_int64
+        images = [vp, i64, vp, i64, i64, i64, C.c_int]
+        L.sid_corr_lattice.argtypes = [C.c_int] + images + [i64] * 7 + [vp] * 3
+        L.sid_corr_lattice_device.argtypes = images + [i64] * 7 + [vp] * 3 + [vp]
+        L.sid_corr_points.argtypes = [C.c_int] + images + [vp] * 3 + [i64, i64] + [vp] * 3
+        L.sid_corr_points_device.argtypes = images + [vp] * 3 + [i64, i64] + [vp] * 3 + [vp]
+        L.sid_corr_last_error.restype = C.c_char_p
+        L.sid_corr_release.argtypes = [C.c_int]
     if hasattr(L, 'sid_prep_apply'):
         vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
         L.sid_prep_subsample.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, C.c_int64, vp, vp]
@@ -270,14 +283,15 @@ def _p(a, t):
 
 def release_workspaces(device=-1):
     """Hand the cached device memory of the detector, the matcher, the first-guess evaluation and the deformation back
-    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``; -1: every device).  No call on that device may be in flight.
+    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``, ``sid_corr_release``; -1: every device).  No call on that device may be in flight.
     A process that never loaded the library has nothing cached: this returns without loading it (it is registered with
     atexit through pmlib.release_contexts, and loading means importing torch and initialising the GPU - not at interpreter
     shutdown, and not in a process that only used the host code)."""
     if _lib is None:
         return
     L = _lib
-    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release', 'sid_warp_release'):
+    for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release', 'sid_warp_release',
+                 'sid_corr_release'):
         if hasattr(L, name):
             getattr(L, name)(int(device))
 
@@ -656,6 +670,7 @@ def _checker(unit, index_error=None):
 _ft_check, _stage_check, _fg_check = _checker('sid_ft'), _checker('sid_stage'), _checker('sid_fg')
 _defor_check, _grid_check, _warp_check = _checker('sid_defor', DEFOR_ERR_INDEX), _checker('sid_grid'), _checker('sid_warp')
 _prep_check, _mask_check, _resize_check = _checker('sid_prep'), _checker('sid_mask'), _checker('sid_resize')
+_corr_check = _checker('sid_corr')
 
 
 def _vp(p):
@@ -955,6 +970,57 @@ def warp_image_device(x, y, xs, ys, valid, rows, cols, src, dtype, src_shape, sr
                                             int(src_shape[1]), int(src_stride), int(out_shape[0]), int(out_shape[1]),
                                             int(order), float(fill), int(diagonal), int(flags), vp[6], int(out_stride),
                                             vp[7], vp[8], vp[9], _vp(stream)))
+
+
+def _corr_outputs(shape, want_r, want_count, want_sums):
+    return (np.empty(shape, dtype=np.float64) if want_r else None, np.empty(shape, dtype=np.int32) if want_count else None,
+            np.empty(tuple(shape) + (5,), dtype=np.int64) if want_sums else None)
+
+
+def _row_stride(img):
+    """Row stride in elements of a 2-D uint8 array with unit inner stride (a single row or no row: its length)."""
+    return img.strides[0] if img.shape[0] > 1 and img.shape[1] > 0 else max(int(img.shape[1]), 0)
+
+
+def corr_lattice(a, b, w, r0, c0, sr, sc, nr, nc, min_count, want_r=True, want_count=False, want_sums=False, device=0):
+    """``sid_corr_lattice`` on host arrays: a, b uint8 [rows, cols] with unit inner stride -> r float64 [nr, nc], count int32
+    [nr, nc], sums int64 [nr, nc, 5] (None where not wanted).  device=-1: the kernels' source in a host loop (tests)."""
+    rows, cols = a.shape
+    r, count, sums = _corr_outputs((int(nr), int(nc)), want_r, want_count, want_sums)
+    if int(nr) * int(nc) == 0 and min(int(nr), int(nc)) >= 0:            # (an empty array has no address to hand over)
+        return r, count, sums
+    _corr_check(lib().sid_corr_lattice(int(device), _vp(a.ctypes.data or 1), _row_stride(a), _vp(b.ctypes.data or 1), _row_stride(b),
+                                       rows, cols, int(w), int(r0), int(c0), int(sr), int(sc), int(nr), int(nc), int(min_count),
+                                       _vp(r), _vp(count), _vp(sums)))
+    return r, count, sums
+
+
+def corr_points(a, b, w, c, r, valid, min_count, want_r=True, want_count=False, want_sums=False, device=0):
+    """``sid_corr_points`` on host arrays: a, b as above; c, r int32 [n] and valid uint8 [n] or None (C-contiguous)
+    -> r float64 [n], count int32 [n], sums int64 [n, 5] (None where not wanted)."""
+    rows, cols = a.shape
+    n = int(c.shape[0])
+    out, count, sums = _corr_outputs((n,), want_r, want_count, want_sums)
+    if n == 0:
+        return out, count, sums
+    _corr_check(lib().sid_corr_points(int(device), _vp(a.ctypes.data or 1), _row_stride(a), _vp(b.ctypes.data or 1), _row_stride(b),
+                                      rows, cols, int(w), _vp(c), _vp(r), _vp(valid), n, int(min_count), _vp(out), _vp(count),
+                                      _vp(sums)))
+    return out, count, sums
+
+
+def corr_lattice_device(a, a_stride, b, b_stride, rows, cols, w, r0, c0, sr, sc, nr, nc, min_count, r, count, sums, stream):
+    """``sid_corr_lattice_device`` on raw device pointers (torch ``data_ptr()``; 0 for an output that is not wanted)."""
+    _corr_check(lib().sid_corr_lattice_device(_vp(a), int(a_stride), _vp(b), int(b_stride), int(rows), int(cols), int(w), int(r0),
+                                              int(c0), int(sr), int(sc), int(nr), int(nc), int(min_count), _vp(r), _vp(count),
+                                              _vp(sums), _vp(stream)))
+
+
+def corr_points_device(a, a_stride, b, b_stride, rows, cols, w, c, r, valid, npts, min_count, out, count, sums, stream):
+    """``sid_corr_points_device`` on raw device pointers (valid 0 for none)."""
+    _corr_check(lib().sid_corr_points_device(_vp(a), int(a_stride), _vp(b), int(b_stride), int(rows), int(cols), int(w), _vp(c),
+                                             _vp(r), _vp(valid), int(npts), int(min_count), _vp(out), _vp(count), _vp(sums),
+                                             _vp(stream)))
 
 
 def _prep_coeffs(coeffs):

@@ -9,6 +9,7 @@ is outside the scope of this package - passing file names raises with a pointer 
 """
 from sea_ice_drift_amd.ftlib import feature_tracking
 from sea_ice_drift_amd.lib import get_drift_vectors, prefetch_triangulation
+from sea_ice_drift_amd.libcorr import local_correlation_at
 from sea_ice_drift_amd.libwarp import warp_image
 from sea_ice_drift_amd.pmlib import pattern_matching
 
@@ -105,3 +106,22 @@ class SeaIceDrift(object):
         if to == 1:
             return warp_image(self.n2[1], x1, y1, x2, y2, out_shape=tuple(self.n1.shape()), **kwargs)
         return warp_image(self.n1[1], x2, y2, x1, y1, out_shape=tuple(self.n2.shape()), **kwargs)
+
+    def get_warp_correlation(self, lons, lats, lon2, lat2, window=35, min_count=None, return_count=False, device=0, **kwargs):
+        """How well the drift field lines the pair up, node by node (not the reference's; ``libcorr``): image 2 is warped into
+        the frame of image 1 (``get_warped_image(..., to=1)``) and correlated with image 1 in a ``window`` x ``window`` square
+        around every node of the grid.
+
+        lons, lats, lon2, lat2 : as in ``get_warped_image``
+        window, min_count, return_count : as in ``libcorr.local_correlation_at``
+        Other keyword arguments are the warp's (``valid=``, ``order=``, ``diagonal=``).
+
+        Returns r with the shape of ``lons`` (NaN at nodes whose position on image 1 is not finite, and where too few
+        pixels of the window hold both images), and the int32 count of usable pixels on request."""
+        import numpy as np
+        warped = self.get_warped_image(lons, lats, lon2, lat2, to=1, device=device, **kwargs)
+        shape = np.shape(lons)
+        x1, y1 = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n1.transform_points(lons, lats, 1)]
+        finite = np.isfinite(x1) & np.isfinite(y1)
+        return local_correlation_at(self.n1[1], warped, np.rint(x1), np.rint(y1), window=window, valid=finite, min_count=min_count,
+                                    return_count=return_count, device=device)
