@@ -6,6 +6,7 @@ keep the reference's call shape: ``pattern_matching`` and ``SeaIceDrift.get_drif
 
 Beside it, not the reference's: ``libfilter``, ``libdefor``, ``libwarp`` (``warp_image``) and ``libcorr``
 (``local_correlation``, ``local_correlation_at``: the local correlation of two uint8 images, e.g. of image 1 with
-the warped image 2).
+the warped image 2) and ``libtrack`` (``map_points``, ``advect``, ``round_trip``: arbitrary points carried through a
+drift grid).
 """
 __version__ = '0.1.0'

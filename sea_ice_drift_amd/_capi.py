@@ -62,6 +62,10 @@ WARP_TILE = (16, 64)                                      # SID_WARP_TILE_ROWS, 
 CORR_SYMBOLS = ('sid_corr_lattice', 'sid_corr_points', 'sid_corr_lattice_device', 'sid_corr_points_device', 'sid_corr_last_error',
                 'sid_corr_release')
 CORR_TILE = (8, 64)                                       # SID_CORR_TILE_ROWS, SID_CORR_TILE_COLS: the nodes of one workgroup
+# include/sid_track.h: arbitrary points mapped through a drift grid
+TRACK_SYMBOLS = ('sid_track_points', 'sid_track_points_device', 'sid_track_last_error', 'sid_track_release')
+TRACK_CLOSED = 1                                          # SID_TRACK_CLOSED
+TRACK_BRUTE_CELLS = 64                                    # SID_TRACK_BRUTE_CELLS: grids below it look at every cell for every point
 
 # every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
 PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
@@ -218,6 +222,12 @@ def lib():
         L.sid_corr_points_device.argtypes = images + [vp] * 3 + [i64, i64] + [vp] * 3 + [vp]
         L.sid_corr_last_error.restype = C.c_char_p
         L.sid_corr_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_track_points'):           # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        vp, i64 = C.c_void_p, C.c_int64
+        L.sid_track_points.argtypes = [C.c_int] + [vp] * 5 + [i64, i64, C.c_int, C.c_uint32, vp, vp, i64, vp, vp, vp]
+        L.sid_track_points_device.argtypes = [vp] * 5 + [i64, i64, C.c_int, C.c_uint32, vp, vp, i64, vp, vp, vp, vp]
+        L.sid_track_last_error.restype = C.c_char_p
+        L.sid_track_release.argtypes = [C.c_int]
     if hasattr(L, 'sid_prep_apply'):
         vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
         L.sid_prep_subsample.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, C.c_int64, vp, vp]
@@ -283,7 +293,7 @@ def _p(a, t):
 
 def release_workspaces(device=-1):
     """Hand the cached device memory of the detector, the matcher, the first-guess evaluation and the deformation back
-    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``, ``sid_corr_release``; -1: every device).  No call on that device may be in flight.
+    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``, ``sid_corr_release``, ``sid_track_release``; -1: every device).  No call on that device may be in flight.
     A process that never loaded the library has nothing cached: this returns without loading it (it is registered with
     atexit through pmlib.release_contexts, and loading means importing torch and initialising the GPU - not at interpreter
     shutdown, and not in a process that only used the host code)."""
@@ -291,7 +301,7 @@ def release_workspaces(device=-1):
         return
     L = _lib
     for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release', 'sid_warp_release',
-                 'sid_corr_release'):
+                 'sid_corr_release', 'sid_track_release'):
         if hasattr(L, name):
             getattr(L, name)(int(device))
 
@@ -670,7 +680,7 @@ def _checker(unit, index_error=None):
 _ft_check, _stage_check, _fg_check = _checker('sid_ft'), _checker('sid_stage'), _checker('sid_fg')
 _defor_check, _grid_check, _warp_check = _checker('sid_defor', DEFOR_ERR_INDEX), _checker('sid_grid'), _checker('sid_warp')
 _prep_check, _mask_check, _resize_check = _checker('sid_prep'), _checker('sid_mask'), _checker('sid_resize')
-_corr_check = _checker('sid_corr')
+_corr_check, _track_check = _checker('sid_corr'), _checker('sid_track')
 
 
 def _vp(p):
@@ -970,6 +980,26 @@ def warp_image_device(x, y, xs, ys, valid, rows, cols, src, dtype, src_shape, sr
                                             int(src_shape[1]), int(src_stride), int(out_shape[0]), int(out_shape[1]),
                                             int(order), float(fill), int(diagonal), int(flags), vp[6], int(out_stride),
                                             vp[7], vp[8], vp[9], _vp(stream)))
+
+
+def track_points(x, y, xs, ys, valid, diagonal, flags, px, py, want_tri=False, device=0):
+    """``sid_track_points`` on host arrays: x, y, xs, ys float64 [R, C] and valid uint8 or None, px, py float64 [n]
+    (C-contiguous all) -> sx, sy float64 [n], tri int32 [n] (None when not wanted).  device=-1: the kernels' source in a host
+    loop (tests)."""
+    rows, cols = x.shape
+    n = int(px.shape[0])
+    sx, sy = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+    tri = np.empty(n, dtype=np.int32) if want_tri else None
+    if n:                                                                # (an empty array has no address to hand over)
+        _track_check(lib().sid_track_points(int(device), *[_vp(a.ctypes.data or 1) for a in (x, y, xs, ys)], _vp(valid), rows, cols,
+                                            int(diagonal), int(flags), _vp(px), _vp(py), n, _vp(sx), _vp(sy), _vp(tri)))
+    return sx, sy, tri
+
+
+def track_points_device(x, y, xs, ys, valid, rows, cols, diagonal, flags, px, py, n, sx, sy, tri, stream):
+    """``sid_track_points_device`` on raw device pointers (torch ``data_ptr()``; valid, tri 0 for none)."""
+    _track_check(lib().sid_track_points_device(*[_vp(q) for q in (x, y, xs, ys, valid)], int(rows), int(cols), int(diagonal),
+                                               int(flags), _vp(px), _vp(py), int(n), _vp(sx), _vp(sy), _vp(tri), _vp(stream)))
 
 
 def _corr_outputs(shape, want_r, want_count, want_sums):

@@ -75,10 +75,9 @@ SID_HD_INLINE unsigned ring(const Nodes &g, int64_t k, double X[4], double Y[4],
     return usable;
 }
 
-// The pixels a cell is examined over: floor(min) - 1 .. ceil(max) + 1 of its usable nodes, clipped to the output.  False when
-// the cell has fewer than three usable nodes or the box is empty.
-SID_HD_INLINE bool box(const double X[4], const double Y[4], unsigned usable, int64_t rows_o, int64_t cols_o,
-                       int64_t &r_lo, int64_t &r_hi, int64_t &c_lo, int64_t &c_hi)
+// floor(min) - 1 .. ceil(max) + 1 of a cell's usable nodes, per axis, before any clip (track_point.h examines a cell for the
+// points in there).  False when the cell has fewer than three usable nodes.
+SID_HD_INLINE bool extent(const double X[4], const double Y[4], unsigned usable, double &cl, double &ch, double &rl, double &rh)
 {
     const int n = (int)(usable & 1) + (int)((usable >> 1) & 1) + (int)((usable >> 2) & 1) + (int)((usable >> 3) & 1);
     if (n < 3) return false;
@@ -89,7 +88,17 @@ SID_HD_INLINE bool box(const double X[4], const double Y[4], unsigned usable, in
             x0 = fmin(x0, X[q]); x1 = fmax(x1, X[q]);
             y0 = fmin(y0, Y[q]); y1 = fmax(y1, Y[q]);
         }
-    double cl = floor(x0) - 1.0, ch = ceil(x1) + 1.0, rl = floor(y0) - 1.0, rh = ceil(y1) + 1.0;
+    cl = floor(x0) - 1.0; ch = ceil(x1) + 1.0; rl = floor(y0) - 1.0; rh = ceil(y1) + 1.0;
+    return true;
+}
+
+// The pixels a cell is examined over: its extent clipped to the output.  False when the cell has fewer than three usable nodes
+// or the box is empty.
+SID_HD_INLINE bool box(const double X[4], const double Y[4], unsigned usable, int64_t rows_o, int64_t cols_o,
+                       int64_t &r_lo, int64_t &r_hi, int64_t &c_lo, int64_t &c_hi)
+{
+    double cl, ch, rl, rh;
+    if (!extent(X, Y, usable, cl, ch, rl, rh)) return false;
     if (cl < 0.0) cl = 0.0;
     if (rl < 0.0) rl = 0.0;
     if (ch > (double)(cols_o - 1)) ch = (double)(cols_o - 1);
@@ -151,10 +160,16 @@ SID_HD_INLINE bool setup_tri(const Cell &cs, int s, Tri &t)
     return true;
 }
 
-SID_HD_INLINE bool inside(const Edge &e, double px, double py)
+// Ed of sid_warp.h: positive on the triangle's side of the edge
+SID_HD_INLINE double edge_side(const Edge &e, double px, double py)
 {
     const double E = e.ex * (py - e.loy) - e.ey * (px - e.lox);
-    const double Ed = e.flip ? -E : E;
+    return e.flip ? -E : E;
+}
+
+SID_HD_INLINE bool inside(const Edge &e, double px, double py)
+{
+    const double Ed = edge_side(e, px, py);
     return Ed > 0.0 || (Ed == 0.0 && e.tie);
 }
 
@@ -164,15 +179,21 @@ SID_HD_INLINE bool owns(const Tri &t, double px, double py)
     return i0 && i1 && i2;
 }
 
-// The source position of pixel centre (px, py) when triangle `t` owns it; false (sx, sy untouched) when it does not
-SID_HD_INLINE bool source(const Tri &t, double px, double py, double &sx, double &sy)
+// The linear interpolant of triangle `t` at (px, py), whoever owns the point (track_point.h asks on its own)
+SID_HD_INLINE void position(const Tri &t, double px, double py, double &sx, double &sy)
 {
-    if (!owns(t, px, py)) return false;
     const double ax = px - t.xa, ay = py - t.ya;
     const double l1 = (ax * t.cy - t.cx * ay) / t.det;
     const double l2 = (t.bx * ay - ax * t.by) / t.det;
     sx = t.sxa + l1 * t.sxb + l2 * t.sxc;
     sy = t.sya + l1 * t.syb + l2 * t.syc;
+}
+
+// The source position of pixel centre (px, py) when triangle `t` owns it; false (sx, sy untouched) when it does not
+SID_HD_INLINE bool source(const Tri &t, double px, double py, double &sx, double &sy)
+{
+    if (!owns(t, px, py)) return false;
+    position(t, px, py, sx, sy);
     return true;
 }
 

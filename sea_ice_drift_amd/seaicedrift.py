@@ -10,6 +10,7 @@ is outside the scope of this package - passing file names raises with a pointer 
 from sea_ice_drift_amd.ftlib import feature_tracking
 from sea_ice_drift_amd.lib import get_drift_vectors, prefetch_triangulation
 from sea_ice_drift_amd.libcorr import local_correlation_at
+from sea_ice_drift_amd.libtrack import map_points, round_trip
 from sea_ice_drift_amd.libwarp import warp_image
 from sea_ice_drift_amd.pmlib import pattern_matching
 
@@ -125,3 +126,52 @@ class SeaIceDrift(object):
         finite = np.isfinite(x1) & np.isfinite(y1)
         return local_correlation_at(self.n1[1], warped, np.rint(x1), np.rint(y1), window=window, valid=finite, min_count=min_count,
                                     return_count=return_count, device=device)
+
+    def track_points(self, lon, lat, lons, lats, lon2, lat2, **kwargs):
+        """Where arbitrary positions on image 1 - buoys, parcels, the nodes of another grid - lie on image 2 according to a
+        drift grid (not the reference's; ``libtrack.map_points``).
+
+        lon, lat : the positions, any one shape
+        lons, lats, lon2, lat2 : as in ``get_warped_image``
+        Other keyword arguments are those of ``libtrack.map_points`` (``valid=``, ``diagonal=``, ``closed=``, ``device=``).
+
+        Returns lon2_pts, lat2_pts with the shape of ``lon``, NaN outside the field."""
+        import numpy as np
+        shape = np.shape(lons)
+        if len(shape) != 2 or any(np.shape(a) != shape for a in (lats, lon2, lat2)):
+            raise ValueError('track_points: lons, lats, lon2, lat2 must be 2-D grids of one shape (got %s)'
+                             % ([np.shape(a) for a in (lons, lats, lon2, lat2)],))
+        if np.shape(lon) != np.shape(lat):
+            raise ValueError('track_points: lon and lat must have one shape (got %s and %s)' % (np.shape(lon), np.shape(lat)))
+        x1, y1 = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n1.transform_points(lons, lats, 1)]
+        x2, y2 = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n2.transform_points(lon2, lat2, 1)]
+        px, py = [np.asarray(a, dtype=np.float64).reshape(np.shape(lon)) for a in self.n1.transform_points(lon, lat, 1)]
+        sx, sy = map_points(x1, y1, x2, y2, px, py, **kwargs)
+        lon_pts, lat_pts = [np.asarray(a, dtype=np.float64).reshape(np.shape(lon)) for a in self.n2.transform_points(sx, sy, 0)]
+        gone = ~(np.isfinite(sx) & np.isfinite(sy))                       # (whatever the projection makes of a NaN pixel)
+        return np.where(gone, np.nan, lon_pts), np.where(gone, np.nan, lat_pts)
+
+    def get_round_trip(self, lons, lats, lon2, lat2, lons_b, lats_b, lon1_b, lat1_b, **kwargs):
+        """The forward-backward check of a drift grid (not the reference's; ``libtrack.round_trip``): every end point of the
+        forward field 1 -> 2 is sent through the backward field 2 -> 1; what comes back is how far it lands from its start.
+
+        lons, lats, lon2, lat2 : the forward field, as in ``get_warped_image``
+        lons_b, lats_b : (Rb, Cb) the grid of start positions on image 2 that ``SeaIceDrift(n2, n1).get_drift_PM`` was given
+        lon1_b, lat1_b : (Rb, Cb) the positions on image 1 it returned (NaN: no result)
+        Other keyword arguments are those of ``libtrack.round_trip`` (``valid=``, ``valid_b=``, ``diagonal=``, ``closed=``,
+        ``device=``).
+
+        Returns dx, dy in pixels of image 1, shaped like ``lons``; NaN where either field has nothing to say."""
+        import numpy as np
+        shape, shape_b = np.shape(lons), np.shape(lons_b)
+        if len(shape) != 2 or any(np.shape(a) != shape for a in (lats, lon2, lat2)):
+            raise ValueError('get_round_trip: lons, lats, lon2, lat2 must be 2-D grids of one shape (got %s)'
+                             % ([np.shape(a) for a in (lons, lats, lon2, lat2)],))
+        if len(shape_b) != 2 or any(np.shape(a) != shape_b for a in (lats_b, lon1_b, lat1_b)):
+            raise ValueError('get_round_trip: lons_b, lats_b, lon1_b, lat1_b must be 2-D grids of one shape (got %s)'
+                             % ([np.shape(a) for a in (lons_b, lats_b, lon1_b, lat1_b)],))
+        x, y = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n1.transform_points(lons, lats, 1)]
+        xs, ys = [np.asarray(a, dtype=np.float64).reshape(shape) for a in self.n2.transform_points(lon2, lat2, 1)]
+        xb, yb = [np.asarray(a, dtype=np.float64).reshape(shape_b) for a in self.n2.transform_points(lons_b, lats_b, 1)]
+        xbs, ybs = [np.asarray(a, dtype=np.float64).reshape(shape_b) for a in self.n1.transform_points(lon1_b, lat1_b, 1)]
+        return round_trip(x, y, xs, ys, xb, yb, xbs, ybs, **kwargs)
