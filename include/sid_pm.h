@@ -185,9 +185,15 @@ int sid_pm_set_points(sid_pm_ctx *ctx, const double *c1, const double *r1, const
 int sid_pm_bind_results(sid_pm_ctx *ctx, double *d_out, int32_t *d_out_ij);
 
 /* Enqueue the kernels for the resident points on the resident pair (asynchronous).  The launches of a run - one per launch class
- * - follow each other on the handle's stream; a SHORT run (all launches together at most 16 rounds of workgroups: a small batch, or
- * a rank's shard of an N-GPU run) puts them side by side on three more non-blocking streams the handle owns (created by
- * sid_pm_create) and joins them on the handle's stream before it returns to it, so the caller sees one stream either way. */
+ * - run on three more non-blocking streams the handle owns (created by sid_pm_create) whenever there are several: the handle's
+ * stream forks to them and joins them before the run returns to it, so the caller sees one stream either way, that stream never
+ * carries a wait of the library's, and events recorded around sid_pm_run bracket the whole run.  A SHORT run (all launches
+ * together at most 16 rounds of workgroups: a small batch, or a rank's shard of an N-GPU run) puts its launches side by side on
+ * them.  Any longer run CHAINS its launches on two of them: launch k + 1 waits (hipStreamWaitValue64 on a word of signal memory the
+ * handle owns) until the last workgroup of launch k has STARTED, and so fills the compute units launch k drains; at most two
+ * launches are in flight.  Chaining needs hipDeviceAttributeCanUseStreamWaitValue and the signal memory (allocated at the first
+ * such run); without either, with SID_PM_NO_CHAIN=1 in the environment, or with a single launch, the launches follow each
+ * other on the handle's stream.  The results do not depend on the order. */
 int sid_pm_run(sid_pm_ctx *ctx);
 /* Wait for the stream; then sid_pm_check. */
 int sid_pm_sync(sid_pm_ctx *ctx);

@@ -90,6 +90,16 @@ struct sid_pm_ctx {
     // side by side on these streams, so that one launch's half-empty last round is filled by the next (sid_pm_run)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t fork_ev = nullptr, join_ev[3] = {nullptr, nullptr, nullptr};
+    // long runs CHAIN their launches on side[0] / side[1] (pm_plan.h chain_rule): launch k + 1 waits - a stream wait on signal
+    // memory - for the word launch k's last-arriving workgroup stores the run's epoch into.  Allocated at the first run that
+    // wants them: the arrival counters of every launch index (zero between runs: the kernels restore them) and one release
+    // word per launch index (an allocation of signal memory is one 64-bit word)
+    bool can_wait_value = false;        // hipDeviceAttributeCanUseStreamWaitValue
+    bool chain_alloc_failed = false;    // the signal memory was refused once: not asked for again
+    uint32_t *chain_count = nullptr;    // [kChainMaxLaunches][kChainWords]
+    unsigned long long *chain_release[sid::kChainMaxLaunches] = {};
+    int n_chain_release = 0;
+    unsigned long long chain_epoch = 1; // chained runs of this handle so far, + 1 (a fresh release word never holds a value a run waits for)
     hipEvent_t slot_ready[2] = {nullptr, nullptr}, slot_done[2] = {nullptr, nullptr};
     bool ready_rec[2] = {false, false}, done_rec[2] = {false, false};
     // resident points: one device arena (a single upload per set_points) carved into the vectors below
@@ -270,6 +280,28 @@ int fill_args(sid_pm_ctx *ctx, const Switches &run_sw, sid::PMArgs &A)
         A.dbg_err = ctx->dbg_err.p;
     }
     return SID_PM_OK;
+}
+
+// The handle's memory for chained launches (sid_pm_ctx::chain_count / chain_release), for runs of up to n launches.  False -
+// and never asked for again - when the runtime refuses it: the run then keeps its launches in sequence.
+bool ensure_chain_memory(sid_pm_ctx *ctx, size_t n)
+{
+    if (ctx->chain_alloc_failed || n > (size_t)sid::kChainMaxLaunches) return false;
+    if (!ctx->chain_count) {
+        const size_t bytes = sizeof(uint32_t) * (size_t)sid::kChainMaxLaunches * sid::kChainWords;
+        if (hipMalloc(reinterpret_cast<void **>(&ctx->chain_count), bytes) != hipSuccess) { ctx->chain_count = nullptr; ctx->chain_alloc_failed = true; }
+        else if (hipMemset(ctx->chain_count, 0, bytes) != hipSuccess) { (void)hipFree(ctx->chain_count); ctx->chain_count = nullptr; ctx->chain_alloc_failed = true; }
+    }
+    while (!ctx->chain_alloc_failed && (size_t)ctx->n_chain_release < n) {
+        void *p = nullptr;
+        if (hipExtMallocWithFlags(&p, sizeof(unsigned long long), hipMallocSignalMemory) != hipSuccess || !p) { ctx->chain_alloc_failed = true; break; }
+        // (host-visible; whatever the runtime initialised the word with, it starts below every epoch: chain_epoch starts at 1
+        // and a run increments it first)
+        __atomic_store_n(static_cast<unsigned long long *>(p), 0ull, __ATOMIC_RELEASE);
+        ctx->chain_release[ctx->n_chain_release++] = static_cast<unsigned long long *>(p);
+    }
+    if (ctx->chain_alloc_failed) (void)hipGetLastError();           // (the refusal is handled here: not the next call's error)
+    return !ctx->chain_alloc_failed;
 }
 
 // The plan of the resident points for the pair that is current now (pm_plan.h: plan_points, with the switches as the
@@ -475,6 +507,8 @@ SID_EXPORT int sid_pm_create(int device, sid_pm_ctx **out)
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&ctx->h_refused), 4 * sizeof(int32_t), hipHostMallocMapped);
         if (e != hipSuccess) { sid_pm_destroy(ctx); return fail(SID_PM_ERR_HIP, "stream/event creation failed: %s", hipGetErrorString(e)); }
         ctx->h_refused[0] = ctx->h_refused[1] = ctx->h_refused[2] = ctx->h_refused[3] = 0;
+        int wait_value = 0;
+        ctx->can_wait_value = hipDeviceGetAttribute(&wait_value, hipDeviceAttributeCanUseStreamWaitValue, device) == hipSuccess && wait_value != 0;
     }
     *out = ctx;
     return SID_PM_OK;
@@ -495,6 +529,8 @@ SID_EXPORT void sid_pm_destroy(sid_pm_ctx *ctx)
         if (ctx->join_ev[k]) (void)hipEventDestroy(ctx->join_ev[k]);
     }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
+    for (int k = 0; k < ctx->n_chain_release; ++k) (void)hipFree(ctx->chain_release[k]);
+    if (ctx->chain_count) (void)hipFree(ctx->chain_count);
     for (auto &pair : ctx->own) for (auto &b : pair) b.release();
     ctx->arena.release();
     sid::lw_workspace_release(ctx->lw); ctx->d_nan_idx.release(); ctx->lw_small.release(); ctx->coef[0].release(); ctx->coef[1].release(); ctx->pre.release();
@@ -654,7 +690,7 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (int rc = classify_points(ctx)) return rc;
     }
-    const Switches run_sw = read_switches();                          // (the four switches of a run: side_by_side, side_first, verbose, debug_check)
+    const Switches run_sw = read_switches();                          // (the five switches of a run: side_by_side, side_first, no_chain, verbose, debug_check)
     const std::vector<Bucket> &buckets = ctx->plan.buckets;
     sid::PMArgs A;
     fill_args(ctx, run_sw, A);
@@ -672,19 +708,41 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
     // and every launch ends with a half-empty round - a quarter of such a run; side by side the next launch's workgroups fill
     // the CUs the previous one drains.  Rule: all launches of a run together are at most kSideRounds rounds of workgroups
     // (side_by_side_rule).  The launches keep their order (largest footprint first).
+    //
+    // LONG runs are CHAINED (pm_plan.h chain_rule): every launch ends with a drain - its last workgroups on a GPU that is
+    // otherwise emptying - and the next launch of the same stream cannot start before the previous one has COMPLETED.  The
+    // starvation above needs workgroups of the earlier launch still waiting to be dispatched, so launch k + 1 is released at
+    // the moment the LAST workgroup of launch k has started (the kernels count their arrival, PMArgs::chain): it fills the
+    // drain slot by slot and competes with nothing.  The launches alternate between side[0] and side[1]; launch k >= 1 is
+    // preceded on its stream by a wait for launch k - 1's release word to reach this run's epoch, and stream order adds
+    // "launch k - 2 has completed": at most two launches in flight.  The handle's stream only forks and joins, as side by
+    // side - the caller's stream, which may be the legacy default stream, never carries a wait.
     bool side_by_side = false;
+    double rounds = 0;
     if (buckets.size() > 1) {
-        double rounds = 0;
         for (const Bucket &b : buckets) rounds += (double)b.count / (256.0 * launch_shape(b, ctx->rp).round_slots);
         side_by_side = side_by_side_rule(run_sw, buckets.size(), rounds);
+    }
+    ChainReason chain_why = chain_reason(run_sw, buckets.size(), rounds, ctx->can_wait_value, true);
+    if (chain_why == kChainYes) chain_why = chain_reason(run_sw, buckets.size(), rounds, ctx->can_wait_value, ensure_chain_memory(ctx, buckets.size()));
+    const bool chained = chain_why == kChainYes;
+    if (run_sw.verbose) {
+        static const char *const kWhy[] = {"", "", "", "", " (not chained: the device lacks stream wait-value support)", " (not chained: no signal memory)"};
+        fprintf(stderr, "sid_pm: launch order %s, %zu launches%s\n", chained ? "chained" : side_by_side ? "side by side" : "sequence", buckets.size(), kWhy[chain_why]);
     }
     // (Switches::side_first, experiments: only the first n launches of a long run side by side - the large-window classes, a
     // round or two of workgroups each - then the rest in sequence)
     int n_side = side_by_side ? (int)buckets.size() : 0;
     if (!side_by_side && run_sw.side_first >= 0) n_side = std::min((int)buckets.size(), run_sw.side_first);
-    if (n_side > 1) HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
+    if (n_side > 1 || chained) HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
     int nb = 0;
     unsigned used = 0;
+    const unsigned long long epoch = chained ? ++ctx->chain_epoch : 0ull;
+    int chain_prev = -1, chain_last = -1;                            // launch index whose release word the next launch waits for; the last launch with points (it releases nobody)
+    if (chained) for (size_t k = 0; k < buckets.size(); ++k) if (buckets[k].count > 0) chain_last = (int)k;
+    // a failure midway: no stream of the handle is left waiting - every release word a wait of this run was enqueued on
+    // gets the epoch from the host (the launch that would have stored it may be the one that failed)
+    auto release_all = [&]() { for (int k = 0; k <= chain_prev; ++k) __atomic_store_n(ctx->chain_release[k], epoch, __ATOMIC_RELEASE); };
     auto join = [&]() -> int {
         for (int k = 0; k < 3; ++k)                                  // the handle's stream continues when every side launch is done
             if (used & (1u << k)) {
@@ -704,6 +762,26 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
             if (!(used & (1u << k))) HIP_TRY(hipStreamWaitEvent(st, ctx->fork_ev, 0));
             used |= 1u << k;
         }
+        A.chain.count = nullptr; A.chain.release = nullptr; A.chain.epoch = 0;
+        if (chained && b.count > 0) {
+            // launch nb of a chained run: side[0] and side[1] in turn, behind the release of the launch before it; it counts
+            // its arrivals unless it is the last (nobody waits for that one's release word)
+            const int k = nb & 1;
+            st = ctx->side[k];
+            hipError_t e = hipSuccess;
+            if (!(used & (1u << k))) e = hipStreamWaitEvent(st, ctx->fork_ev, 0);
+            used |= 1u << k;
+            if (e == hipSuccess && chain_prev >= 0) e = hipStreamWaitValue64(st, ctx->chain_release[chain_prev], epoch, hipStreamWaitValueGte);
+            if (e != hipSuccess) {
+                release_all();
+                (void)join();
+                return fail(SID_PM_ERR_HIP, "chained launch: stream wait failed: %s", hipGetErrorString(e));
+            }
+            if (nb != chain_last) {
+                A.chain.count = ctx->chain_count + (size_t)nb * sid::kChainWords; A.chain.release = ctx->chain_release[nb]; A.chain.epoch = epoch;
+            }
+        }
+        const int this_launch = nb;
         ++nb;
         A.order = ctx->d_order + b.offset;
         A.gsii_off = ctx->d_goff.p ? ctx->d_goff.p + b.offset : nullptr;
@@ -718,9 +796,11 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
                           ? sid::launch_pm_rp(A, lds_launch, nthreads, b.band, b.big ? 0 : ctx->rp_paired, b.pitch, b.occ, st, b.big)
                           : sid::launch_pm_mfma(A, lds_launch, nthreads, b.band, use_paired(ctx->plan.sw, ctx->n_angles), st);
         if (e != 0) {
+            release_all();
             (void)join();                                            // (what the side streams already hold still orders before the handle's stream)
             return fail(SID_PM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         }
+        if (A.chain.count) chain_prev = this_launch;                 // (the next launch waits for this one's release word)
     }
     if (int rc = join()) return rc;
     if (int rc = run_large_points(ctx, A)) return rc;
@@ -1184,6 +1264,9 @@ SID_EXPORT int sid_pm_estimate_residency(const double *border, int64_t n, int im
 // shards tools/shard_sim.py measures: 1.0 / 0.7 / 0.5 / 0.5 rounds for 1 / 2 / 3 / 4 workgroups per CU) - a launch shorter than
 // one round still takes a full one; a SHORT run (side_by_side_rule, the launcher's own) ends with ONE tail, the longest, and
 // SID_DIST_TAIL_BLEND (0.7) of the others; the points of the large-window pipeline run one after the other behind the launches.
+// LONG runs are priced as a sequence, although the launcher chains them (chain_rule: the next launch fills the previous one's
+// drain): only shards long enough not to be short are affected, rebalance_with_feedback measures those anyway, and the tail
+// constants are refitted once tails under chaining have been measured.
 SID_EXPORT int sid_pm_estimate_run_time(const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, double *time_ns)
 {
     if (!time_ns || n < 0 || (n > 0 && !border)) return fail(SID_PM_ERR_ARG, "bad argument");

@@ -13,6 +13,26 @@ constexpr uint32_t kSubpixel = 128u;    // SID_PM_SUBPIXEL (include/sid_pm.h), b
 // waits for one memory round trip (launch position -> record) instead of two (position -> index -> five vectors).
 struct PointRec { int32_t pt; uint32_t gsii_off; double c1, r1, c2fg, r2fg, border; };
 
+// Chained launches (sid_pm_run, pm_plan.h chain_rule): every workgroup of a chained launch counts its ARRIVAL first thing in the
+// kernel, and the one that completes the count releases the stream the next launch waits on - the next launch starts while
+// this one drains, but only once this one has nothing left to dispatch.  The count is sharded (one word takes about 88 adds
+// per microsecond; a launch starts 1024 workgroups in less than one): kChainShards words on 128-byte lines, shard =
+// blockIdx.x & 7, and a ninth word that counts the completed shards.  The shard sizes follow from n_launch alone
+// (chain_shard_count), so "my add returned size - 1" identifies a shard's last arrival without a second read.
+constexpr int kChainShards = 8;
+constexpr int kChainLineWords = 32;                                   // u32 words per 128-byte line
+constexpr int kChainWords = (kChainShards + 1) * kChainLineWords;     // arrival counters of ONE launch: eight shards + the shard count
+constexpr int kChainMaxLaunches = 64;                                 // release words / counter blocks per handle
+// workgroups i in [0, n) with (i & 7) == j
+__host__ __device__ inline int chain_shard_count(int n, int j) { return n > j ? (n - j + kChainShards - 1) / kChainShards : 0; }
+__host__ __device__ inline int chain_nonempty_shards(int n) { return n < kChainShards ? (n > 0 ? n : 0) : kChainShards; }
+
+struct PMChain {
+    uint32_t *count;                // [kChainWords] arrival counters of this launch, device memory, zero between runs; null: not chained
+    unsigned long long *release;    // this launch's release word (signal memory, host-visible): receives `epoch` when the last workgroup has arrived
+    unsigned long long epoch;       // count of chained runs of the handle: never wraps, never reset
+};
+
 // Arguments of one launch (one block per grid point of this launch).
 struct PMArgs {
     const uint8_t *img1; int64_t rows1, cols1, stride1;
@@ -81,6 +101,7 @@ struct PMArgs {
     uint32_t *ring;
     uint32_t *pool;                                 // [kPoolBlocks][pool_stride u32]
     uint32_t pool_stride;
+    PMChain chain;                                  // chained launches (above); all zero: not chained (debug_point, the large-window pipeline, single launches)
     // diagnostics (debug_point only; null in production launches)
     uint8_t *dbg_templates; float *dbg_ccm; float *dbg_hes; int32_t *dbg_shape; int64_t dbg_cap;
     long long *dbg_cycles;                          // [32] shader-clock stamps at phase boundaries

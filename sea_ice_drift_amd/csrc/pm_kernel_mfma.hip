@@ -1874,6 +1874,24 @@ __device__ __noinline__ void ph_hessian_fast(unsigned flags, int iy, int ix, flo
     if (tid == 0) { m->red_f[0] = (h - med) / std_from_sums(tx, txx, npos); m->red_f[1] = best_r; }
 }
 
+// ---- chained launches (PMArgs::chain, pm_kernel.h): ONE lane per workgroup counts the workgroup's arrival ----
+// chain_count issues the add on the workgroup's shard; chain_settle looks at what it returned.  The shard's last arrival adds
+// one to the ninth word, and the arrival that completes the non-empty shards is the launch's last: it puts the zeros back
+// (nobody else touches the nine words again in this run) and stores the epoch into the release word.  Relaxed: no payload
+// travels with the flag.  Agent scope for the counters; the release word lives in host-visible signal memory: system scope.
+// A function of uniform arguments that is NOT inlined: the kernels' prologues keep their register allocation (inlined, the
+// same lines cost several instantiations of the row-pair kernel up to five spilled VGPRs: profiles/r09_registers.txt).
+__device__ __noinline__ void chain_arrive(u32 *count, unsigned long long *release, unsigned long long epoch, int n_launch)
+{
+    const int shard = (int)(blockIdx.x & (u32)(kChainShards - 1));
+    const u32 before = __hip_atomic_fetch_add(count + shard * kChainLineWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((int)before + 1 != chain_shard_count(n_launch, shard)) return;
+    const u32 shards = __hip_atomic_fetch_add(count + kChainShards * kChainLineWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((int)shards + 1 != chain_nonempty_shards(n_launch)) return;
+    for (int k = 0; k <= kChainShards; ++k) __hip_atomic_store(count + k * kChainLineWords, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(release, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // BAND = 4: up to 768 threads, three wavefronts per SIMD (168 VGPRs).  BAND = 8: 256 threads, two per SIMD (the
 // class whose LDS footprint admits two workgroups per CU anyway): an 8-row band halves the LDS bytes per MFMA.
 template <int S, int BAND, bool PAIRED>
@@ -1883,6 +1901,9 @@ __global__ __launch_bounds__(BAND == 8 ? 512 : kMaxBlockM, BAND == 8 ? 2 : kOccM
     MiscM *m = reinterpret_cast<MiscM *>(smem);
     Geo *G = reinterpret_cast<Geo *>(smem + kGeoOff);
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // chained launch: this workgroup's arrival, counted once by lane 0 of the last wavefront and settled HERE, above every
+    // return of the kernel - a workgroup that left uncounted would leave a stream waiting for ever
+    if (A.chain.count != nullptr && tid == (int)blockDim.x - 64) chain_arrive(A.chain.count, A.chain.release, A.chain.epoch, A.n_launch);
     const int pt = A.order[blockIdx.x];
     const int s = S > 0 ? S : A.img_size, K = A.n_angles;
 

@@ -1770,6 +1770,10 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
         stack = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u) * (u32)kRingWordsPerXcd + (((u32)blockIdx.x >> 3) & (u32)(kRingHomeWords - 1));
         peek = ring_peek(A.ring, stack);
     }
+    // chained launch (PMArgs::chain): this workgroup's arrival, counted once, by the lane that waits for a round trip here
+    // anyway - lane 0 of the last wavefront, pool or no pool; the add goes out while the peek above is in flight.  Counted
+    // and settled HERE, above every return of the kernel: a workgroup that left uncounted would leave a stream waiting for ever
+    if (A.chain.count != nullptr && tid == (int)blockDim.x - 64) chain_arrive(A.chain.count, A.chain.release, A.chain.epoch, A.n_launch);
 #define SID_STAMP(k) do { if (A.dbg_cycles && tid == 0) A.dbg_cycles[k] = (long long)clock64(); } while (0)
     SID_STAMP(0);
 

@@ -50,6 +50,7 @@ struct Switches {
     bool samp2 = false;             // SID_PM_SAMP2=1: build the sampling table sorted per angle (set_points).  tests/test_gpu_samp2.py
     int side_by_side = -1;          // per run.  SID_PM_SIDE_BY_SIDE=0 / 1: launches never / always side by side; -1 (unset): side_by_side_rule.  A/B runs
     int side_first = -1;            // per run.  SID_PM_SIDE_FIRST=n: only the first n launches of a long run side by side.  A/B runs
+    bool no_chain = false;          // per run.  SID_PM_NO_CHAIN=1: the launches of a long run one after the other, never chained (chain_rule).  tests/test_gpu_chained_launches.py
     bool verbose = false;           // per run.  SID_PM_VERBOSE=1: one line per launch on stderr.  tests/test_gpu_launch_classes.py, bench.py
     bool debug_check = false;       // per run.  SID_PM_DEBUG_CHECK=1: debugging builds compare their sums on the device
     double tail_blend = 0.7;        // SID_DIST_TAIL_BLEND=x: share of the other launches' tails a SHORT run pays (sid_pm_estimate_run_time).  A/B runs
@@ -81,6 +82,7 @@ inline Switches read_switches()
     w.samp2 = on("SID_PM_SAMP2");
     if ((e = getenv("SID_PM_SIDE_BY_SIDE"))) w.side_by_side = atoi(e) > 0 ? 1 : 0;
     if ((e = getenv("SID_PM_SIDE_FIRST"))) w.side_first = std::max(0, atoi(e));
+    w.no_chain = on("SID_PM_NO_CHAIN");
     w.verbose = on("SID_PM_VERBOSE");
     w.debug_check = on("SID_PM_DEBUG_CHECK");
     if ((e = getenv("SID_DIST_TAIL_BLEND"))) w.tail_blend = atof(e);
@@ -133,6 +135,26 @@ inline bool side_by_side_rule(const Switches &sw, size_t n_launches, double roun
 {
     if (n_launches < 2) return false;
     return sw.side_by_side >= 0 ? sw.side_by_side > 0 : rounds <= kSideRounds;
+}
+
+// Launches of a LONG run are CHAINED (sid_pm_run): launch k + 1 is released when the last workgroup of launch k has STARTED
+// (the kernels count their arrival: PMArgs::chain), so it fills the CUs launch k drains and never competes with workgroups
+// of launch k that still wait to be dispatched - what made whole launches side by side slower.  The release is a stream wait
+// on signal memory, a beta interface of the runtime: the device must report it (hipDeviceAttributeCanUseStreamWaitValue)
+// and the handle must have got its signal memory.  SID_PM_SIDE_FIRST (experiments) keeps its own order.
+enum ChainReason { kChainYes = 0, kChainSingle, kChainShort, kChainSwitch, kChainNoWaitValue, kChainNoSignalMemory };
+inline ChainReason chain_reason(const Switches &sw, size_t n_launches, double rounds, bool can_wait_value, bool have_signal_memory)
+{
+    if (n_launches < 2) return kChainSingle;
+    if (side_by_side_rule(sw, n_launches, rounds) || sw.side_first >= 0) return kChainShort;
+    if (sw.no_chain) return kChainSwitch;
+    if (!can_wait_value) return kChainNoWaitValue;
+    if (!have_signal_memory) return kChainNoSignalMemory;
+    return kChainYes;
+}
+inline bool chain_rule(const Switches &sw, size_t n_launches, double rounds, bool can_wait_value, bool have_signal_memory)
+{
+    return chain_reason(sw, n_launches, rounds, can_wait_value, have_signal_memory) == kChainYes;
 }
 
 // paired: the kernel's two-row-phase sweep for angle sets of at most kPairedMaxAngles (pm_kernel.h)
