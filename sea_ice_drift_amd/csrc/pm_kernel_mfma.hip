@@ -40,6 +40,7 @@
 #include <math.h>
 #include <type_traits>
 #include "pm_kernel.h"
+#include "ncc_norm.h"
 
 namespace sid {
 
@@ -370,83 +371,45 @@ __device__ __forceinline__ float std_from_sums(double sx, double sxx, int n) {
 }
 
 
-// The spec's normalisation in IEEE double -> float32 (shared by candidates and the winner's matrix).
-__device__ __forceinline__ float exact_ncc(double numer, double dI, double rTd, bool constT, bool lowvar)
-{
-    if (constT) return 1.0f;
-    if (lowvar) return 0.0f;
-    const double rI = 1.0 / sqrt(dI);
-    double q = numer * rI;
-    q = q * rTd;
-    const double aq = fabs(q);
-    return aq < 1.0 ? (float)q : (aq < 1.125 ? (q > 0.0 ? 1.0f : -1.0f) : 0.0f);
-}
-
+// The spec's normalisation in IEEE double -> float32 (shared by candidates and the winner's matrix): ncc_norm.h, which the
+// host check (tests/cpp/ncc_norm_check.cpp) compiles as well.
 __device__ __forceinline__ float exact_from_sums(int p, int swp, u32 siiv, double nd, double sT, double rTd, bool cT)
 {
-    const double swd = (double)swp, siid = (double)siiv;
-    const double dI = nd * siid - swd * swd;                           // exact
-    const double s2 = siid + 256.0 * swd + 16384.0 * nd;               // S_II in the uint8 domain
-    const bool lowvar = (2.0 * dI <= nd) && (dI * 8388608.0 <= 10.0 * nd * s2);
-    const double numer = nd * (double)p - swd * sT;                    // exact
-    return exact_ncc(numer, dI, rTd, cT, lowvar);
+    return ncc_norm::spec_from_sums(p, swp, siiv, nd, sT, rTd, cT);
 }
 
 // The same value by a shorter route (the winner's matrix evaluates thousands of these per point).  1 / sqrt(dI) comes
 // from v_rsq_f64 and two coupled Newton steps - no IEEE square root, no IEEE division - so the product q' differs from
 // the spec's q (whose own 1 / sqrt carries two roundings) by less than 2^-49 |q|.  (float)q' = (float)q unless q' lies
 // that close to a rounding boundary of float32 (the middle of the 29 discarded mantissa bits) or to one of the clamp
-// thresholds 1 and 1.125: those lanes - about 1e-7 of them, plus the perfect matches - take the spec's route.
-__device__ __forceinline__ float exact_from_sums_fast(int p, int swp, u32 siiv, double nd, double sT, double rTd, bool cT)
+// thresholds 1 and 1.125: those lanes - about 1e-7 of them, plus the perfect matches - take the spec's route; lanes beyond
+// a threshold take the clamp.  The arithmetic is ncc_norm.h's; this is its seed.
+struct RsqSeed { __device__ __forceinline__ double operator()(double x) const { return __builtin_amdgcn_rsq(x); } };
+
+// one value start to end; spec_route: whether the specification's route decided it (the selftest counts those)
+__device__ __forceinline__ float exact_from_sums_fast(int p, int swp, u32 siiv, double nd, double sT, double rTd, bool cT, bool &spec_route)
 {
-    const double swd = (double)swp, siid = (double)siiv;
-    const double dI = nd * siid - swd * swd;                           // exact
-    const double numer = nd * (double)p - swd * sT;                    // exact
-    bool slow = 2.0 * dI <= nd;                                        // the low-variance rule needs a second look
-    const double x = slow ? 1.0 : dI;
-    const double y0 = __builtin_amdgcn_rsq(x);
-    double g = x * y0, h = 0.5 * y0;
-    double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
-    r = __builtin_fma(-h, g, 0.5);
-    h = __builtin_fma(h, r, h);                                        // 1 / (2 sqrt(dI))
-    const double q = (numer * h) * (2.0 * rTd);
-    const double aq = fabs(q);
-    const u32 lo29 = (u32)__double2loint(q) & 0x1fffffffu;
-    slow |= (lo29 - (0x10000000u - 64u)) <= 128u;
-    slow |= fabs(aq - 1.0) < 1e-13 || fabs(aq - 1.125) < 1e-13;
-    float out = aq < 1.0 ? (float)q : (aq < 1.125 ? (q > 0.0 ? 1.0f : -1.0f) : 0.0f);
-    if (cT) out = 1.0f;
-    if (slow && !cT) out = exact_from_sums(p, swp, siiv, nd, sT, rTd, cT);
-    return out;
+    return ncc_norm::from_sums_fast(p, swp, siiv, nd, sT, rTd, cT, RsqSeed(), spec_route);
 }
 
-// Branch-free part of exact_from_sums_fast: the value by the short route and whether the lane must take the spec's route
-// instead.  Callers evaluate a batch of these back to back (independent dependency chains interleave) and handle the rare
-// flagged ones afterwards - a branch around every single value serialises the ~20-deep double-precision chains.
-__device__ __forceinline__ float ncc_fast_nobranch(int p, int swp, u32 siiv, double nd, double sT, double rTd, bool cT, bool &slow)
+// Branch-free part of it (ncc_norm::lean): the value by the short route and whether the lane needs a second look
+// (ncc_flagged).  Callers evaluate a batch of these back to back (independent dependency chains interleave) and handle the
+// rare flagged ones afterwards - a branch around every single value serialises the ~20-deep double-precision chains.  The
+// caller hoists `c` (ncc_norm::Hoisted) and handles a constant template on its own.
+__device__ __forceinline__ float ncc_fast_nobranch(int p, int swp, u32 siiv, const ncc_norm::Hoisted &c, bool &flagged)
 {
-    const double swd = (double)swp, siid = (double)siiv;
-    const double dI = nd * siid - swd * swd;                           // exact
-    const double numer = nd * (double)p - swd * sT;                    // exact
-    bool sl = 2.0 * dI <= nd;                                          // the low-variance rule needs a second look
-    const double x = sl ? 1.0 : dI;
-    const double y0 = __builtin_amdgcn_rsq(x);
-    double g = x * y0, h = 0.5 * y0;
-    double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
-    r = __builtin_fma(-h, g, 0.5);
-    h = __builtin_fma(h, r, h);                                        // 1 / (2 sqrt(dI))
-    const double q = (numer * h) * (2.0 * rTd);
-    const double aq = fabs(q);
-    const u32 lo29 = (u32)__double2loint(q) & 0x1fffffffu;
-    sl |= (lo29 - (0x10000000u - 64u)) <= 128u;
-    sl |= fabs(aq - 1.0) < 1e-13 || fabs(aq - 1.125) < 1e-13;
-    const float clamp = aq < 1.125 ? (q > 0.0 ? 1.0f : -1.0f) : 0.0f;
-    float out = aq < 1.0 ? (float)q : clamp;
-    out = cT ? 1.0f : out;
-    slow = sl && !cT;
-    return out;
+    double q;
+    return ncc_norm::lean(p, swp, siiv, c, RsqSeed(), flagged, q);
+}
+// A flagged value, behind the batch: q' is computed again from sums the compiler cannot relate to the batch's (it would
+// otherwise keep every q' and 1 / sqrt(dI) of the batch in registers for a block that almost never runs: 51 spilled VGPRs
+// instead of 24 in the 128-register build)
+__device__ __forceinline__ float ncc_flagged(int p, int swp, u32 siiv, const ncc_norm::Hoisted &c, double rTd)
+{
+    asm volatile("" : "+v"(p), "+v"(swp));
+    bool fl, spec_route; double q;
+    (void)ncc_norm::lean(p, swp, siiv, c, RsqSeed(), fl, q);
+    return ncc_norm::flagged_value(p, swp, siiv, c, rTd, q, spec_route);
 }
 
 struct Score { float lmax, bestv; int bestkey; };
@@ -2069,13 +2032,10 @@ __global__ void ncc_selftest_kernel(unsigned long long seed, int per_thread, int
         const double target = f * sqrt(dI > 0 ? dI : 0.0) * sqrt(dT);
         const int p = (int)llrint((target + (double)swp * (double)sT) / nd);
         const float a = exact_from_sums(p, swp, siiv, nd, (double)sT, rTd, false);
-        const float b = exact_from_sums_fast(p, swp, siiv, nd, (double)sT, rTd, false);
+        bool spec_route;
+        const float b = exact_from_sums_fast(p, swp, siiv, nd, (double)sT, rTd, false, spec_route);
         bad += __float_as_uint(a) != __float_as_uint(b) ? 1ull : 0ull;
-        // (the count of spec-route evaluations is re-derived: same predicate as in exact_from_sums_fast)
-        const double y = 1.0 / sqrt(dI > 0 ? dI : 1.0);
-        const double q = ((nd * (double)p - (double)swp * (double)sT) * y) * rTd, aq = fabs(q);
-        const u32 lo29 = (u32)__double2loint(q) & 0x1fffffffu;
-        slow += (2.0 * dI <= nd || (lo29 - (0x10000000u - 64u)) <= 128u || fabs(aq - 1.0) < 1e-13 || fabs(aq - 1.125) < 1e-13) ? 1ull : 0ull;
+        slow += spec_route ? 1ull : 0ull;
     }
     atomicAdd(&out[0], (unsigned long long)per_thread);
     if (bad) atomicAdd(&out[1], bad);

@@ -1473,20 +1473,28 @@ __device__ __forceinline__ void rp_winner_item(int y0, int x0, const double sT, 
             sv[k][r] = ONES ? aS1[r] : swv[k][r];
         }
     }
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            bool sl;
-            res[k][r] = ncc_fast_nobranch(pv[k][r], sv[k][r], siv[k][r], nd, sT, rT, cT, sl);
-            slowbits |= (sl && idxv[k][r] >= 0) ? (1u << (4 * k + r)) : 0u;
-        }
-    if (slowbits) {                                                    // rare: low-variance windows, rounding boundaries, |q| at a clamp threshold
+    if (cT) {                                                          // a constant template: 1 everywhere (uniform for the angle)
 #pragma unroll
         for (int k = 0; k < NT; ++k)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if ((slowbits >> (4 * k + r)) & 1u) res[k][r] = exact_from_sums(pv[k][r], sv[k][r], siv[k][r], nd, sT, rT, cT);
+            for (int r = 0; r < 4; ++r) res[k][r] = 1.0f;
+    } else {
+        const ncc_norm::Hoisted hc = ncc_norm::Hoisted::make(nd, sT, rT);
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bool sl;
+                res[k][r] = ncc_fast_nobranch(pv[k][r], sv[k][r], siv[k][r], hc, sl);
+                slowbits |= (sl && idxv[k][r] >= 0) ? (1u << (4 * k + r)) : 0u;
+            }
+        if (slowbits) {                                                // rare: low-variance windows, rounding boundaries, |q| at or beyond a clamp threshold
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if ((slowbits >> (4 * k + r)) & 1u) res[k][r] = ncc_flagged(pv[k][r], sv[k][r], siv[k][r], hc, rT);
+        }
     }
 #pragma unroll
     for (int k = 0; k < NT; ++k)
@@ -1571,20 +1579,28 @@ __device__ __forceinline__ void rp_winx_pass(int tile0, int tstep, int ntx, cons
     if (!GS) fetch_sii();
     float res[NT][4];
     u32 slowbits = 0;
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            bool sl;
-            res[k][r] = ncc_fast_nobranch(acc[k][r], ONES ? acc1[k][r] : swv[k][r], siv[k][r], nd, sT, rT, cT, sl);
-            slowbits |= (sl && idxv[k][r] >= 0) ? (1u << (4 * k + r)) : 0u;
-        }
-    if (slowbits) {                                                    // rare: low-variance windows, rounding boundaries, |q| at a clamp threshold
+    if (cT) {                                                          // a constant template: 1 everywhere (uniform for the angle)
 #pragma unroll
         for (int k = 0; k < NT; ++k)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if ((slowbits >> (4 * k + r)) & 1u) res[k][r] = exact_from_sums(acc[k][r], ONES ? acc1[k][r] : swv[k][r], siv[k][r], nd, sT, rT, cT);
+            for (int r = 0; r < 4; ++r) res[k][r] = 1.0f;
+    } else {
+        const ncc_norm::Hoisted hc = ncc_norm::Hoisted::make(nd, sT, rT);
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bool sl;
+                res[k][r] = ncc_fast_nobranch(acc[k][r], ONES ? acc1[k][r] : swv[k][r], siv[k][r], hc, sl);
+                slowbits |= (sl && idxv[k][r] >= 0) ? (1u << (4 * k + r)) : 0u;
+            }
+        if (slowbits) {                                                // rare: low-variance windows, rounding boundaries, |q| at or beyond a clamp threshold
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if ((slowbits >> (4 * k + r)) & 1u) res[k][r] = ncc_flagged(acc[k][r], ONES ? acc1[k][r] : swv[k][r], siv[k][r], hc, rT);
+        }
     }
 #pragma unroll
     for (int k = 0; k < NT; ++k)
@@ -1663,6 +1679,7 @@ __device__ __noinline__ void rp_winner_kept(int ka, const u32 *gs)
     const u32 *acc = gs + G.gsa;
     float *ccm = reinterpret_cast<float *>(smem + G.ccm_off);
     constexpr int kB = 4;                                              // values per thread and batch: independent double-precision chains interleave
+    const ncc_norm::Hoisted hc = ncc_norm::Hoisted::make(nd, sT, rT);
     for (int base = 0; base < npos; base += kB * kBlockM) {
         int idx[kB], pv[kB], sv[kB]; u32 si[kB]; float res[kB];
 #pragma unroll
@@ -1679,16 +1696,21 @@ __device__ __noinline__ void rp_winner_kept(int ka, const u32 *gs)
             si[u] = sii_at(gs, i);
         }
         u32 slowbits = 0;
+        if (cT) {                                                      // a constant template: 1 everywhere
 #pragma unroll
-        for (int u = 0; u < kB; ++u) {
-            bool sl;
-            res[u] = ncc_fast_nobranch(pv[u], sv[u], si[u], nd, sT, rT, cT, sl);
-            slowbits |= (sl && idx[u] < npos) ? (1u << u) : 0u;
-        }
-        if (slowbits) {                                                // rare: low-variance windows, rounding boundaries, |q| at a clamp threshold
+            for (int u = 0; u < kB; ++u) res[u] = 1.0f;
+        } else {
 #pragma unroll
-            for (int u = 0; u < kB; ++u)
-                if ((slowbits >> u) & 1u) res[u] = exact_from_sums(pv[u], sv[u], si[u], nd, sT, rT, cT);
+            for (int u = 0; u < kB; ++u) {
+                bool sl;
+                res[u] = ncc_fast_nobranch(pv[u], sv[u], si[u], hc, sl);
+                slowbits |= (sl && idx[u] < npos) ? (1u << u) : 0u;
+            }
+            if (slowbits) {                                            // rare: low-variance windows, rounding boundaries, |q| at or beyond a clamp threshold
+#pragma unroll
+                for (int u = 0; u < kB; ++u)
+                    if ((slowbits >> u) & 1u) res[u] = ncc_flagged(pv[u], sv[u], si[u], hc, rT);
+            }
         }
 #pragma unroll
         for (int u = 0; u < kB; ++u)
