@@ -71,6 +71,25 @@ int sid_fg_distance_image(int device, const double *seeds, int64_t n_seeds, int6
 int sid_fg_knn(int device, const double *seeds, int64_t n_seeds, const double *values, const double *q, int64_t n_q,
                int k, double max_dist, double *out, int32_t *count, int32_t *index);
 
+/* Queries that are not finite (a NaN or an infinite coordinate; a projection does not keep grid points finite outside its
+ * footprint).  sid_fg_interp_linear: such a query is in no simplex and near none - out = NaN, simplex = -1, doubt = 0 - on the
+ * bucket route and on the brute-force route alike.  sid_fg_nearest_dist: its distance is +inf on both routes (every comparison
+ * with a distance that is not a number is false, and no finite seed is nearer than +inf).  No cell arithmetic is undefined
+ * for them: a coordinate that is not a number falls into cell 0 of the buckets, an infinite one into a border cell. */
+
+/* Test support (host values only, no device call; the ABI version does not count it): the route of the calling thread's last
+ * sid_fg_interp_linear, sid_fg_nearest_dist, sid_fg_distance_image or sid_fg_knn (on a device) that succeeded.
+ *   buckets    1: the queries walked the buckets; 0: every simplex / every seed
+ *   entries    interpolation: the bucket entries counted (more than `capacity`: they did not fit, brute force; 0 where the
+ *              buckets were not tried: SID_FG_NO_GRID, a box without area); seeds: the seeds binned (0: none)
+ *   capacity   the room of the bucket lists: 8 n_simp + 128 * 128, or the number of (usable) seeds
+ *   ychunks, chunk   brute-force point location: the simplex chunks of the launch and the simplices per chunk (else 0)
+ * SID_PM_ERR_ARG: out NULL; SID_PM_ERR_STATE: no such call yet on this thread. */
+typedef struct sid_fg_route {
+    int64_t buckets, entries, capacity, ychunks, chunk;
+} sid_fg_route;
+int sid_fg_debug_route(struct sid_fg_route *out);
+
 const char *sid_fg_last_error(void);
 /* Free the grow-only device scratch block of the two entry points on `device` (every device: -1).  The blocks are kept between calls so that no call pays for
  * hipMalloc / hipFree; a long-lived process that is done with the GPU hands the memory back with this (the Python mirror's

@@ -41,6 +41,18 @@ int sid_ft_knn2_device(const uint8_t *d_desc1, int64_t n1, const uint8_t *d_desc
                        int32_t *d_idx, int32_t *d_dist, void *d_workspace, void *hip_stream);
 int64_t sid_ft_workspace_bytes(int64_t n1, int64_t n2);
 
+/* Test support (host arithmetic only, no device call; the ABI version does not count it): the plan sid_ft_knn2_device follows
+ * for n1 queries and n2 train descriptors, as csrc/ft_plan.h computes it - SID_FT_NO_MFMA is read at the time of the call.
+ *   mfma      1: the int8-MFMA form (n1 * n2 >= 2^24 and n2 >= 1024, SID_FT_NO_MFMA unset); 0: one thread per query
+ *   chunk     train descriptors per chunk (MFMA form: a multiple of 256, counted in the padded set)
+ *   nchunks   chunks, = the second dimension of the launch
+ *   n1pad, n2pad   MFMA form: the set sizes padded to multiples of 256; else n1, n2 themselves
+ * SID_PM_ERR_ARG: out NULL or a negative size; SID_PM_ERR_UNSUPPORTED: n1 > (2^31 - 1) / 4 or n2 >= 2^22, as the device entry. */
+typedef struct sid_ft_plan {
+    int64_t mfma, chunk, nchunks, n1pad, n2pad;
+} sid_ft_plan;
+int sid_ft_debug_plan(int64_t n1, int64_t n2, struct sid_ft_plan *out);
+
 const char *sid_ft_last_error(void);
 /* Free the grow-only device scratch block of sid_ft_knn2 on `device` (every device: -1).  The blocks are kept between calls so that no call pays for
  * hipMalloc / hipFree; a long-lived process that is done with the GPU hands the memory back with this (the Python mirror's

@@ -30,7 +30,7 @@ SYMBOLS = (
 )
 
 # every symbol include/sid_ft.h declares (feature-tracking matcher, same library)
-FT_SYMBOLS = ('sid_ft_knn2', 'sid_ft_knn2_device', 'sid_ft_workspace_bytes', 'sid_ft_last_error', 'sid_ft_release')
+FT_SYMBOLS = ('sid_ft_knn2', 'sid_ft_knn2_device', 'sid_ft_workspace_bytes', 'sid_ft_debug_plan', 'sid_ft_last_error', 'sid_ft_release')
 
 # every symbol include/sid_stage.h declares (uint8 staging, same library)
 STAGE_SYMBOLS = ('sid_stage_create', 'sid_stage_destroy', 'sid_stage_begin', 'sid_stage_begin_hint', 'sid_stage_order_stats_ws',
@@ -41,7 +41,8 @@ STAGE_SYMBOLS = ('sid_stage_create', 'sid_stage_destroy', 'sid_stage_begin', 'si
 ORB_SYMBOLS = ('sid_orb_detect', 'sid_orb_last_error', 'sid_orb_release')
 
 # every symbol include/sid_fg.h declares (first-guess evaluation, same library)
-FG_SYMBOLS = ('sid_fg_interp_linear', 'sid_fg_nearest_dist', 'sid_fg_distance_image', 'sid_fg_knn', 'sid_fg_last_error', 'sid_fg_release')
+FG_SYMBOLS = ('sid_fg_interp_linear', 'sid_fg_nearest_dist', 'sid_fg_distance_image', 'sid_fg_knn', 'sid_fg_debug_route', 'sid_fg_last_error',
+              'sid_fg_release')
 
 # every symbol include/sid_defor.h declares (deformation on a triangulation, same library)
 DEFOR_SYMBOLS = ('sid_defor_triangulation', 'sid_defor_elems', 'sid_defor_triangulation_device', 'sid_defor_elems_device',
@@ -155,6 +156,8 @@ def lib():
     L.sid_ft_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.sid_ft_workspace_bytes.restype = C.c_int64
     L.sid_ft_last_error.restype = C.c_char_p
+    if hasattr(L, 'sid_ft_debug_plan'):          # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        L.sid_ft_debug_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p]
     L.sid_stage_count_valid.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
     L.sid_stage_order_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int,
                                         _f32p, C.c_void_p]
@@ -181,6 +184,8 @@ def lib():
     if hasattr(L, 'sid_fg_knn'):                 # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
         L.sid_fg_knn.argtypes = [C.c_int, _f64p, C.c_int64, _f64p, _f64p, C.c_int64, C.c_int, C.c_double, _f64p, _i32p, _i32p]
     L.sid_fg_last_error.restype = C.c_char_p
+    if hasattr(L, 'sid_fg_debug_route'):         # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        L.sid_fg_debug_route.argtypes = [C.c_void_p]
     if hasattr(L, 'sid_defor_triangulation'):
         vp = C.c_void_p
         L.sid_defor_triangulation.argtypes = [C.c_int] + [_f64p] * 4 + [C.c_int64, vp, C.c_int, C.c_int64] + [_f64p] * 5
@@ -702,6 +707,45 @@ def ft_knn2(desc1, desc2, device=0):
     _ft_check(L.sid_ft_knn2(int(device), d1.ctypes.data_as(_u8p), len(d1), d2.ctypes.data_as(_u8p), len(d2),
                             idx.ctypes.data_as(_i32p), dist.ctypes.data_as(_i32p)))
     return idx, dist
+
+
+class _FtPlan(C.Structure):
+    """struct sid_ft_plan (include/sid_ft.h)."""
+    _fields_ = [(name, C.c_int64) for name in ('mfma', 'chunk', 'nchunks', 'n1pad', 'n2pad')]
+
+
+def ft_debug_plan(n1, n2):
+    """The plan sid_ft_knn2_device follows for n1 x n2 descriptors (include/sid_ft.h sid_ft_debug_plan; test support, no
+    device call): a dict of the struct's fields."""
+    s = _FtPlan()
+    _ft_check(lib().sid_ft_debug_plan(int(n1), int(n2), C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in _FtPlan._fields_}
+
+
+def ft_workspace_bytes(n1, n2):
+    """Bytes of workspace ft_knn2_device needs for n1 x n2 descriptors (include/sid_ft.h sid_ft_workspace_bytes)."""
+    return int(lib().sid_ft_workspace_bytes(int(n1), int(n2)))
+
+
+def ft_knn2_device(d_desc1, n1, d_desc2, n2, d_idx, d_dist, d_workspace, stream=0):
+    """ft_knn2 on device-resident buffers, asynchronous on ``stream`` (include/sid_ft.h sid_ft_knn2_device): raw device
+    addresses of desc1 [n1,32] and desc2 [n2,32] uint8 (16-byte aligned), idx and dist [n1,2] int32, and a workspace of
+    ft_workspace_bytes(n1, n2) bytes (16-byte aligned)."""
+    _ft_check(lib().sid_ft_knn2_device(_vp(d_desc1), int(n1), _vp(d_desc2), int(n2), _vp(d_idx), _vp(d_dist), _vp(d_workspace),
+                                       _vp(stream)))
+
+
+class _FgRoute(C.Structure):
+    """struct sid_fg_route (include/sid_fg.h)."""
+    _fields_ = [(name, C.c_int64) for name in ('buckets', 'entries', 'capacity', 'ychunks', 'chunk')]
+
+
+def fg_debug_route():
+    """Which route the calling thread's last first-guess call took (include/sid_fg.h sid_fg_debug_route; test support): a
+    dict of the struct's fields."""
+    s = _FgRoute()
+    _fg_check(lib().sid_fg_debug_route(C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in _FgRoute._fields_}
 
 
 class _StageRoute(C.Structure):

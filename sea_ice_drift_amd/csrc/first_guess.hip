@@ -67,13 +67,14 @@ __global__ __launch_bounds__(256) void k_locate(const Simp *simp, int64_t ns, in
     const double x = i < nq ? q[2 * i] : 0.0, y = i < nq ? q[2 * i + 1] : 0.0;
     const double eps = 100.0 * DBL_EPSILON;
     const int64_t k0 = (int64_t)blockIdx.y * chunk, k1 = k0 + chunk < ns ? k0 + chunk : ns;
+    const bool live = i < nq && isfinite(x) && isfinite(y);             // (a query that is not finite is in no simplex: k_locate_grid)
     bool found = false, close = false;
     for (int64_t base = k0; base < k1; base += kTile) {
         __syncthreads();
         if (base + (int64_t)threadIdx.x < k1) tile[threadIdx.x] = simp[base + threadIdx.x];
         __syncthreads();
         const int n = (int)((k1 - base) < kTile ? (k1 - base) : kTile);
-        if (!found && i < nq) {
+        if (!found && live) {
             for (int k = 0; k < n; ++k) {
                 const Simp &s = tile[k];
                 const double dx = x - s.rx, dy = y - s.ry;
@@ -120,13 +121,15 @@ __global__ void k_eval(const Simp *simp, const int32_t *loc, const int32_t *near
 // A simplex is listed in every cell its bounding box - widened by far more than the location tolerance kTol can reach -
 // touches; cell indices come from ONE monotone function of the coordinate (cell_of), for simplices and queries alike, so a
 // query that lies within kTol of a simplex finds it in the list of its own cell.  Queries outside the box are clamped to the
-// border cells (they can only be outside the hull, or within kTol of it).
+// border cells (they can only be outside the hull, or within kTol of it); a coordinate that is not a number goes to cell 0, where
+// every comparison with it is false: such a query is in no simplex and infinitely far from every seed.
 constexpr int kGrid = 128;
 struct GridGeo { double x0, y0, ix, iy; };
 __device__ __forceinline__ int cell_of(double v, double v0, double inv)
 {
     const double c = floor((v - v0) * inv);
-    return c < 0.0 ? 0 : (c > (double)(kGrid - 1) ? kGrid - 1 : (int)c);
+    if (!(c > 0.0)) return 0;                                          // (not a number too: a total function, as track_bucket.h's)
+    return c > (double)(kGrid - 1) ? kGrid - 1 : (int)c;
 }
 __device__ __forceinline__ void simplex_cells(const double *pts, const int32_t *simp, int64_t k, const GridGeo g, int &cx0, int &cx1, int &cy0, int &cy1)
 {
@@ -183,6 +186,10 @@ __global__ __launch_bounds__(256) void k_locate_grid(const Simp *simp, const int
     if (i >= nq) return;
     const double x = q[2 * i], y = q[2 * i + 1];
     const double eps = 100.0 * DBL_EPSILON;
+    // A query that is not finite is in no simplex and near none.  Left to the arithmetic an INFINITE one is "contained" wherever
+    // the transform has a zero for its coordinate (0 * inf is NaN, which fmin ignores) - in the lowest such simplex of all on the
+    // brute-force route, of its border cell only on this one: the routes would differ.
+    if (!(isfinite(x) && isfinite(y))) { loc[i] = 0x7f7f7f7f; near[i] = 0; return; }
     const int cell = cell_of(y, g.y0, g.iy) * kGrid + cell_of(x, g.x0, g.ix);
     int32_t best = 0x7f7f7f7f;
     bool close = false;
@@ -436,6 +443,9 @@ void knn_launch(const KnnArgs &a)
 // and three of them cost about as much as the kernels).  Calls are serialised by the pool's mutex.
 DevicePool<> g_pool;
 
+// what sid_fg_debug_route reports: host values only, written where a call succeeds
+thread_local sid_fg_route g_route = {-1, 0, 0, 0, 0};
+
 struct Box {
     double x_lo = INFINITY, x_hi = -INFINITY, y_lo = INFINITY, y_hi = -INFINITY;
     void add(double x, double y) { x_lo = fmin(x_lo, x); x_hi = fmax(x_hi, x); y_lo = fmin(y_lo, y); y_hi = fmax(y_hi, y); }
@@ -484,17 +494,20 @@ SID_EXPORT int sid_fg_interp_linear(int device, const double *pts, int64_t n_pts
     HIP_TRY(hipMemcpyAsync(d_simp, simplices, sizeof(int32_t) * 3 * n_simp, hipMemcpyHostToDevice, 0));
     hipLaunchKernelGGL(k_transform, dim3((unsigned)((n_simp + 255) / 256)), dim3(256), 0, 0, d_pts, d_simp, n_simp, d_t);
     const unsigned qb = (unsigned)((n_q + 255) / 256), sb = (unsigned)((n_simp + 255) / 256);
+    int32_t total = 0;
+    sid_fg_route route = {0, 0, grid_cap, 0, 0};
     if (use_grid) {
         // bucket lists: count, prefix sums, fill; the total decides whether they fit (one 4-byte read-back)
-        int32_t total = 0;
         HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (kGrid * kGrid + 1), 0));
         hipLaunchKernelGGL(k_grid_build<0>, dim3(sb), dim3(256), 0, 0, d_pts, d_simp, d_t, n_simp, geo, d_cnt, d_start, d_ids, grid_cap);
         hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, 0, d_cnt, d_start);
         HIP_TRY(hipMemcpy(&total, d_start + kGrid * kGrid, sizeof total, hipMemcpyDeviceToHost));
         if ((int64_t)total <= grid_cap) hipLaunchKernelGGL(k_grid_build<1>, dim3(sb), dim3(256), 0, 0, d_pts, d_simp, d_t, n_simp, geo, d_cnt, d_start, d_ids, grid_cap);
         else use_grid = false;
+        route.entries = total;
     }
     if (use_grid) {
+        route.buckets = 1;
         hipLaunchKernelGGL(k_locate_grid, dim3(qb), dim3(256), 0, 0, d_t, d_start, d_ids, geo, d_q, n_q, d_loc, d_near);
     } else {
         unsigned ychunks = qb >= 2048 ? 1u : (2048u + qb - 1) / qb;                 // aim at >= 2048 blocks
@@ -502,6 +515,7 @@ SID_EXPORT int sid_fg_interp_linear(int device, const double *pts, int64_t n_pts
         if ((int64_t)ychunks > tiles) ychunks = (unsigned)tiles;
         const int64_t chunk = ((tiles + ychunks - 1) / ychunks) * kTile;
         ychunks = (unsigned)((n_simp + chunk - 1) / chunk);
+        route.ychunks = ychunks; route.chunk = chunk;
         HIP_TRY(hipMemsetAsync(d_loc, 0x7f, sizeof(int32_t) * n_q, 0));             // 0x7f7f7f7f: above any index
         HIP_TRY(hipMemsetAsync(d_near, 0, sizeof(int32_t) * n_q, 0));
         hipLaunchKernelGGL(k_locate, dim3(qb, ychunks), dim3(256), 0, 0, d_t, n_simp, chunk, d_q, n_q, d_loc, d_near);
@@ -518,6 +532,15 @@ SID_EXPORT int sid_fg_interp_linear(int device, const double *pts, int64_t n_pts
     HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 2 * n_q, hipMemcpyDeviceToHost));    // (synchronous: the host arrays are the caller's)
     HIP_TRY(hipStreamSynchronize(0));
     s.done();
+    g_route = route;
+    return SID_PM_OK;
+}
+
+SID_EXPORT int sid_fg_debug_route(struct sid_fg_route *out)
+{
+    if (!out) return fail(SID_PM_ERR_ARG, "null route");
+    if (g_route.buckets < 0) return fail(SID_PM_ERR_STATE, "debug_route needs a call that succeeded on this thread first");
+    *out = g_route;
     return SID_PM_OK;
 }
 
@@ -575,6 +598,7 @@ int nearest_dist_impl(int device, const double *seeds, int64_t n_seeds, const do
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(dist, d_d, sizeof(double) * n_q, hipMemcpyDeviceToHost));
     s.done();
+    g_route = sid_fg_route{grid ? 1 : 0, grid ? n_seeds : 0, n_seeds, 0, 0};
     return SID_PM_OK;
 }
 
@@ -635,6 +659,7 @@ int knn_on_device(int device, const double *seeds, const double *values, int64_t
     HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 2 * n_q, hipMemcpyDeviceToHost));   // (synchronous: the host arrays are the caller's)
     HIP_TRY(hipStreamSynchronize(0));
     s.done();
+    g_route = sid_fg_route{grid ? 1 : 0, grid ? n_use : 0, n_use, 0, 0};
     return SID_PM_OK;
 }
 

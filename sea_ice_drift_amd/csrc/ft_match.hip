@@ -22,13 +22,14 @@
 #include <stdlib.h>
 
 #include "../../include/sid_ft.h"
+#include "ft_plan.h"
 #include "host_util.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kNone = 0xffffffffu;
-constexpr int64_t kMaxTrain = (int64_t)1 << 22;             // index bits of the key
+// the plan - which form, the chunks, the regions of the workspace, the size limits - is plain C++: ft_plan.h
+using sid_ft::kThreads; using sid_ft::kNone; using sid_ft::kMaxTrain; using sid_ft::kQB; using sid_ft::kTB;
+using sid_ft::MfmaPlan; using sid_ft::plan; using sid_ft::plan_mfma; using sid_ft::use_mfma;
 
 __device__ __forceinline__ void push(uint32_t &k1, uint32_t &k2, uint32_t key)
 {
@@ -69,8 +70,6 @@ __global__ __launch_bounds__(kThreads) void ft_knn2_partial(const uint4 *__restr
 // MFMA form
 // ---------------------------------------------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
-constexpr int kQB = 256;            // queries per workgroup
-constexpr int kTB = 256;            // train descriptors per LDS batch
 constexpr int kRowB = 288;          // LDS bytes per expanded descriptor: 256 + 32 (slot of lane (n, kg) = 2 n + kg mod 16: distinct in every ds_read_b128 lane group)
 
 // one byte per bit: E[d][8 b + k] = bit k of byte b of descriptor d (rows n .. npad-1 zero); 8 output bytes per thread
@@ -205,49 +204,31 @@ __global__ __launch_bounds__(kThreads) void ft_knn2_merge(const uint32_t *__rest
     dist[2 * q + 1] = k2 == kNone ? -1 : (int32_t)(k2 >> 22);
 }
 
-// chunk size: enough blocks to fill the chip (>= ~2048 blocks), at least 256 train descriptors per chunk
-void plan(int64_t n1, int64_t n2, int &chunk, int &nchunks)
-{
-    const int64_t qblocks = (n1 + kThreads - 1) / kThreads;
-    int64_t want = std::max<int64_t>(1, (2048 + qblocks - 1) / std::max<int64_t>(qblocks, 1));
-    int64_t c = std::max<int64_t>(256, (n2 + want - 1) / want);
-    c = std::min<int64_t>(c, std::max<int64_t>(n2, 1));
-    chunk = (int)c;
-    nchunks = (int)((n2 + c - 1) / c);
-    if (nchunks < 1) nchunks = 1;
-}
-
-// MFMA form: queries and train descriptors padded to 256; chunks of whole LDS batches, >= ~512 workgroups (two per CU)
-struct MfmaPlan { int64_t n1pad, n2pad; int chunk, nchunks; size_t off_e1, off_e2, off_c, total; };
-constexpr int64_t kMfmaMinPairs = (int64_t)1 << 24;                    // below this the one-thread-per-query kernel is as fast
-bool use_mfma(int64_t n1, int64_t n2) { return n1 * n2 >= kMfmaMinPairs && n2 >= 1024 && getenv("SID_FT_NO_MFMA") == nullptr; }
-MfmaPlan plan_mfma(int64_t n1, int64_t n2)
-{
-    MfmaPlan P;
-    P.n1pad = (std::max<int64_t>(n1, 1) + kQB - 1) / kQB * kQB; P.n2pad = (std::max<int64_t>(n2, 1) + kTB - 1) / kTB * kTB;   // (empty sets: sized, never run)
-    const int64_t qblocks = P.n1pad / kQB, batches = P.n2pad / kTB;
-    int64_t want = std::max<int64_t>(1, (512 + qblocks - 1) / qblocks);
-    want = std::min<int64_t>(want, batches);
-    const int64_t per = (batches + want - 1) / want;
-    P.chunk = (int)(per * kTB); P.nchunks = (int)((batches + per - 1) / per);
-    P.off_e1 = up(sizeof(uint32_t) * 2 * (size_t)std::max<int64_t>(n1, 1) * P.nchunks);
-    P.off_e2 = P.off_e1 + (size_t)P.n1pad * 256;
-    P.off_c = P.off_e2 + (size_t)P.n2pad * 256;
-    P.total = P.off_c + up(sizeof(uint32_t) * (size_t)P.n2pad);
-    return P;
-}
-
 }  // namespace
 
 SID_EXPORT const char *sid_ft_last_error(void) { return g_err; }
 
 SID_EXPORT int64_t sid_ft_workspace_bytes(int64_t n1, int64_t n2)
 {
-    if (n1 < 0 || n2 < 0) return 0;
-    int chunk, nchunks;
-    plan(n1, n2, chunk, nchunks);
-    const int64_t valu = (int64_t)sizeof(uint32_t) * 2 * std::max<int64_t>(n1, 1) * nchunks;
-    return std::max<int64_t>(valu, (int64_t)plan_mfma(n1, n2).total);      // (either kernel may run: SID_FT_NO_MFMA, size)
+    return sid_ft::workspace_bytes(n1, n2);
+}
+
+// Test support: the plan sid_ft_knn2_device follows for these sizes.  Host arithmetic only.
+SID_EXPORT int sid_ft_debug_plan(int64_t n1, int64_t n2, struct sid_ft_plan *out)
+{
+    if (!out) return fail(SID_PM_ERR_ARG, "null plan");
+    if (n1 < 0 || n2 < 0) return fail(SID_PM_ERR_ARG, "negative descriptor count");
+    if (!sid_ft::sizes_supported(n1, n2))
+        return fail(SID_PM_ERR_UNSUPPORTED, "at most %lld train descriptors", (long long)kMaxTrain - 1);
+    if (use_mfma(n1, n2)) {
+        const MfmaPlan P = plan_mfma(n1, n2);
+        *out = sid_ft_plan{1, P.chunk, P.nchunks, P.n1pad, P.n2pad};
+    } else {
+        int chunk, nchunks;
+        plan(n1, n2, chunk, nchunks);
+        *out = sid_ft_plan{0, chunk, nchunks, n1, n2};
+    }
+    return SID_PM_OK;
 }
 
 SID_EXPORT int sid_ft_knn2_device(const uint8_t *d_desc1, int64_t n1, const uint8_t *d_desc2, int64_t n2,
@@ -256,7 +237,7 @@ SID_EXPORT int sid_ft_knn2_device(const uint8_t *d_desc1, int64_t n1, const uint
     if (n1 < 0 || n2 < 0) return fail(SID_PM_ERR_ARG, "negative descriptor count");
     if (n1 == 0) return SID_PM_OK;
     if (!d_desc1 || !d_idx || !d_dist || !d_workspace || (n2 > 0 && !d_desc2)) return fail(SID_PM_ERR_ARG, "null pointer");
-    if (n1 > 0x7fffffff / 4 || n2 >= kMaxTrain)
+    if (!sid_ft::sizes_supported(n1, n2))
         return fail(SID_PM_ERR_UNSUPPORTED, "at most %lld train descriptors", (long long)kMaxTrain - 1);
     if ((reinterpret_cast<uintptr_t>(d_desc1) | reinterpret_cast<uintptr_t>(d_desc2)) & 15)
         return fail(SID_PM_ERR_ARG, "descriptors must be 16-byte aligned");

@@ -6,6 +6,7 @@ from scipy.interpolate import LinearNDInterpolator
 from scipy.spatial import Delaunay, cKDTree
 
 from sea_ice_drift_amd import _capi, lib, pmlib as my
+from tests import fg_spec
 from tests.golden import make_golden as mg
 
 pytestmark = pytest.mark.gpu
@@ -75,8 +76,10 @@ def test_lattice_keypoints_are_resolved_or_flagged():
 def test_bucket_walk_equals_the_brute_force_pass(monkeypatch):
     """Round 4: point location walks a uniform grid of buckets instead of testing every simplex.  Values, located simplices
     and doubt flags must be those of the brute-force pass (SID_FG_NO_GRID=1) on scattered and on lattice key points, with
-    queries inside, outside, on vertices and far outside the bounding box; a triangulation whose bucket lists would not fit
-    (one huge sliver fan) falls back to the brute-force pass by itself."""
+    queries inside, outside, on vertices and far outside the bounding box; and on a huge sliver fan, long thin triangles across
+    the whole box.  (The fan's lists still fit - 24 162 entries in room for 64 384, asserted below against the count of
+    tests/fg_spec.py - so it walks the buckets; a triangulation whose lists do not fit falls back to the brute-force pass by
+    itself in tests/test_gpu_fg_small.py: the square of two triangles and the small sliver fan.)"""
     rng = np.random.default_rng(28)
     cases = []
     src = rng.uniform(0, 9000, (30000, 2))
@@ -92,6 +95,11 @@ def test_bucket_walk_equals_the_brute_force_pass(monkeypatch):
         tri = Delaunay(src)
         monkeypatch.delenv('SID_FG_NO_GRID', raising=False)
         got, sx, doubt = _capi.fg_interp_linear(tri.points, tri.simplices, vals, q, details=True)
+        if src is far:                                                    # the route it took: the lists are counted, and walked where they fit
+            entries, capacity = fg_spec.bucket_entries(tri.points, tri.simplices, np.ones(len(tri.simplices), dtype=bool))
+            route = _capi.fg_debug_route()
+            assert (route['buckets'], route['entries'], route['capacity']) == (int(entries <= capacity), entries, capacity)
+            assert (entries, capacity) == (24162, 8 * 6000 + 128 * 128)
         monkeypatch.setenv('SID_FG_NO_GRID', '1')
         exp, esx, edoubt = _capi.fg_interp_linear(tri.points, tri.simplices, vals, q, details=True)
         monkeypatch.delenv('SID_FG_NO_GRID')

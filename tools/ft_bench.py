@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Matcher benchmark: the reference notebook's case (examples/simple.ipynb cell 2: 24 183 x 22 694 ORB
 descriptors matched in 3.42 s by cv2.BFMatcher on unknown hardware) on sid_ft_knn2.  Prints one JSON line."""
-import ctypes as C, json, os, sys, time
+import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,15 +14,13 @@ d1 = rng.integers(0, 256, (n1, 32), dtype=np.uint8)
 d2 = rng.integers(0, 256, (n2, 32), dtype=np.uint8)
 t0 = time.perf_counter(); idx, dist = _capi.ft_knn2(d1, d2); t_host = time.perf_counter() - t0
 t0 = time.perf_counter(); idx, dist = _capi.ft_knn2(d1, d2); t_host = min(t_host, time.perf_counter() - t0)
-L = _capi.lib()
 dev = torch.device('cuda:0')
 a, b = torch.from_numpy(d1).to(dev), torch.from_numpy(d2).to(dev)
 oi = torch.empty((n1, 2), dtype=torch.int32, device=dev); od = torch.empty_like(oi)
-ws = torch.empty(int(L.sid_ft_workspace_bytes(n1, n2)), dtype=torch.uint8, device=dev)
+ws = torch.empty(_capi.ft_workspace_bytes(n1, n2), dtype=torch.uint8, device=dev)
 st = torch.cuda.current_stream().cuda_stream
 def run():
-    rc = L.sid_ft_knn2_device(a.data_ptr(), n1, b.data_ptr(), n2, oi.data_ptr(), od.data_ptr(), ws.data_ptr(), st)
-    assert rc == 0, L.sid_ft_last_error()
+    _capi.ft_knn2_device(a.data_ptr(), n1, b.data_ptr(), n2, oi.data_ptr(), od.data_ptr(), ws.data_ptr(), st)
 run(); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
@@ -36,7 +34,7 @@ ok = bool(np.array_equal(eidx, idx[:m]) and np.array_equal(edist, dist[:m]))
 pairs = float(n1) * n2
 print(json.dumps({'metric': 'Hamming kNN (k=2) descriptor match', 'n1': n1, 'n2': n2,
                   'kernel_ms': t_kernel * 1e3, 'pairs_per_s': pairs / t_kernel,
-                  'form': 'mfma (256 int8 MACs + 4 VALU lane-ops per pair)' if pairs >= 2 ** 24 and n2 >= 1024 and not os.environ.get('SID_FT_NO_MFMA')
+                  'form': 'mfma (256 int8 MACs + 4 VALU lane-ops per pair)' if _capi.ft_debug_plan(n1, n2)['mfma']
                           else 'one thread per query (21 VALU lane-ops per pair: 8 xor + 8 bcnt + key + 3 min/max)',
                   'host_call_ms_incl_alloc_and_pcie': t_host * 1e3,
                   'numpy_oracle_s_extrapolated_from_%d_queries' % m: t_cpu, 'parity_vs_oracle_sample': ok,
