@@ -20,6 +20,7 @@
 #include "pm_kernel.h"
 #include "pm_large.h"
 #include "pm_plan.h"
+#include "pm_host.h"
 
 using namespace sid::plan;   // the launch planner: Switches, Plan, Bucket and the decision functions
 
@@ -56,21 +57,13 @@ struct Image {
     int64_t rows = 0, cols = 0, stride = 0;
 };
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return SID_PM_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(T)));
-        cap = n;
-        return SID_PM_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+// device memory that frees itself where it leaves its scope (pm_host.h), on the device that is current there: the entry points
+// declare their buffers after their Guard
+struct HipAlloc {
+    static int alloc(void **p, size_t bytes) { HIP_TRY(hipMalloc(p, bytes)); return SID_PM_OK; }
+    static void free(void *p) { (void)hipFree(p); }
 };
+template <typename T> using DevBuf = ScopedBuf<T, HipAlloc>;
 
 }  // namespace
 
@@ -87,10 +80,10 @@ struct sid_pm_ctx {
     // slot_done[s] = last kernels reading slot s complete (an upload into s waits for it)
     hipStream_t copy_stream = nullptr;
     // short runs (a rank's shard of an N-GPU run: two or three launches of a few rounds of workgroups each) put their launches
-    // side by side on these streams, so that one launch's half-empty last round is filled by the next (sid_pm_run)
+    // side by side on these streams, so that one launch's half-empty last round is filled by the next (pm_plan.h launch_schedule)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t fork_ev = nullptr, join_ev[3] = {nullptr, nullptr, nullptr};
-    // long runs CHAIN their launches on side[0] / side[1] (pm_plan.h chain_rule): launch k + 1 waits - a stream wait on signal
+    // long runs CHAIN their launches on side[0] / side[1] (pm_plan.h launch_schedule): launch k + 1 waits - a stream wait on signal
     // memory - for the word launch k's last-arriving workgroup stores the run's epoch into.  Allocated at the first run that
     // wants them: the arrival counters of every launch index (zero between runs: the kernels restore them) and one release
     // word per launch index (an allocation of signal memory is one 64-bit word)
@@ -258,12 +251,18 @@ void gauss_taps(double w5[5])
     for (int k = 0; k < 5; ++k) w5[k] = w[k] / sum;
 }
 
+// the current pair as the kernels take it (the resident points' launches and debug_point)
+void set_images(const sid_pm_ctx *ctx, sid::PMArgs &A)
+{
+    A.img1 = ctx->cur[0].ptr; A.rows1 = ctx->cur[0].rows; A.cols1 = ctx->cur[0].cols; A.stride1 = ctx->cur[0].stride;
+    A.img2 = ctx->cur[1].ptr; A.rows2 = ctx->cur[1].rows; A.cols2 = ctx->cur[1].cols; A.stride2 = ctx->cur[1].stride;
+}
+
 int fill_args(sid_pm_ctx *ctx, const Switches &run_sw, sid::PMArgs &A)
 {
     memset(&A, 0, sizeof A);
     gauss_taps(A.gauss_w);
-    A.img1 = ctx->cur[0].ptr; A.rows1 = ctx->cur[0].rows; A.cols1 = ctx->cur[0].cols; A.stride1 = ctx->cur[0].stride;
-    A.img2 = ctx->cur[1].ptr; A.rows2 = ctx->cur[1].rows; A.cols2 = ctx->cur[1].cols; A.stride2 = ctx->cur[1].stride;
+    set_images(ctx, A);
     const int64_t n = ctx->n;
     A.c1 = ctx->d_vec; A.r1 = ctx->d_vec + n; A.c2fg = ctx->d_vec + 2 * n; A.r2fg = ctx->d_vec + 3 * n;
     A.border = ctx->d_vec + 4 * n;
@@ -531,12 +530,9 @@ SID_EXPORT void sid_pm_destroy(sid_pm_ctx *ctx)
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     for (int k = 0; k < ctx->n_chain_release; ++k) (void)hipFree(ctx->chain_release[k]);
     if (ctx->chain_count) (void)hipFree(ctx->chain_count);
-    for (auto &pair : ctx->own) for (auto &b : pair) b.release();
-    ctx->arena.release();
-    sid::lw_workspace_release(ctx->lw); ctx->d_nan_idx.release(); ctx->lw_small.release(); ctx->coef[0].release(); ctx->coef[1].release(); ctx->pre.release();
-    ctx->out.release(); ctx->out_ij.release(); ctx->dbg_err.release(); ctx->gsii.release(); ctx->d_goff.release(); ctx->d_rec.release(); ctx->ring.release(); ctx->pool.release();
+    sid::lw_workspace_release(ctx->lw);
     if (ctx->h_refused) (void)hipHostFree(ctx->h_refused);
-    delete ctx;
+    delete ctx;                                                       // (the DevBuf members free themselves, on the handle's device: `g` is still in scope)
 }
 
 SID_EXPORT int sid_pm_set_stream(sid_pm_ctx *ctx, void *hip_stream)
@@ -633,30 +629,27 @@ SID_EXPORT int sid_pm_set_points(sid_pm_ctx *ctx, const double *c1, const double
     // it executes a third fewer VALU instructions in the template phase: built on request only, SID_PM_SAMP2=1)
     if (!sampv.empty() && use_rp(sw, s) && sw.samp2) make_samp2(sampv, K, s, samp2v);
 
-    // one arena, one upload: [5n doubles | K angles | 4K rotation terms | order (int32 n) | sampling table]
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_vec = 0, o_ang = up(o_vec + sizeof(double) * 5 * (size_t)n), o_rot = up(o_ang + sizeof(double) * (size_t)K),
-                 o_ord = up(o_rot + sizeof(double) * 4 * (size_t)K), o_smp = up(o_ord + sizeof(int32_t) * (size_t)n),
-                 o_smp2 = up(o_smp + sizeof(uint16_t) * (sampv.size() + 4)), total = up(o_smp2 + sizeof(uint32_t) * samp2v.size());
+    // one arena, one upload: the layout of pm_host.h measures it, carves the host image and carves the device block
+    auto layout = [&](Carver &c) { return point_arena(c, (size_t)n, (size_t)K, sampv.size(), samp2v.size()); };
+    Carver measure;
+    layout(measure);
+    const size_t total = measure.off;
     HIP_TRY(hipStreamSynchronize(ctx->stream));               // nothing may still read the old arena
     if (int rc = ctx->arena.reserve(total)) return rc;
     if (int rc = ctx->out.reserve((size_t)(5 * n))) return rc;
     if (int rc = ctx->out_ij.reserve((size_t)(3 * n))) return rc;
     std::vector<uint8_t> host(total, 0);
+    Carver on_host(host.data()), on_device(ctx->arena.p);
+    const PointArena h = layout(on_host), d = layout(on_device);
     const double *src[5] = {c1, r1, c2fg, r2fg, border};
-    for (int k = 0; k < 5 && n > 0; ++k) memcpy(host.data() + o_vec + sizeof(double) * (size_t)(k * n), src[k], sizeof(double) * (size_t)n);
-    memcpy(host.data() + o_ang, angles, sizeof(double) * (size_t)K);
-    memcpy(host.data() + o_rot, rotv.data(), sizeof(double) * rotv.size());
-    if (!sampv.empty()) memcpy(host.data() + o_smp, sampv.data(), sizeof(uint16_t) * sampv.size());
-    if (!samp2v.empty()) memcpy(host.data() + o_smp2, samp2v.data(), sizeof(uint32_t) * samp2v.size());
+    for (int k = 0; k < 5 && n > 0; ++k) memcpy(h.vec + (size_t)(k * n), src[k], sizeof(double) * (size_t)n);
+    memcpy(h.angles, angles, sizeof(double) * (size_t)K);
+    memcpy(h.rot, rotv.data(), sizeof(double) * rotv.size());
+    if (!sampv.empty()) memcpy(h.samp, sampv.data(), sizeof(uint16_t) * sampv.size());
+    if (!samp2v.empty()) memcpy(h.samp2, samp2v.data(), sizeof(uint32_t) * samp2v.size());
     // synchronous: the host vectors are caller-owned and not retained
     HIP_TRY(hipMemcpy(ctx->arena.p, host.data(), total, hipMemcpyHostToDevice));
-    ctx->d_vec = reinterpret_cast<double *>(ctx->arena.p + o_vec);
-    ctx->d_angles = reinterpret_cast<double *>(ctx->arena.p + o_ang);
-    ctx->d_rot = reinterpret_cast<double *>(ctx->arena.p + o_rot);
-    ctx->d_order = reinterpret_cast<int32_t *>(ctx->arena.p + o_ord);
-    ctx->d_samp = reinterpret_cast<uint16_t *>(ctx->arena.p + o_smp);
-    ctx->d_samp2 = samp2v.empty() ? nullptr : reinterpret_cast<uint32_t *>(ctx->arena.p + o_smp2);
+    ctx->d_vec = d.vec; ctx->d_angles = d.angles; ctx->d_rot = d.rot; ctx->d_order = d.order; ctx->d_samp = d.samp; ctx->d_samp2 = d.samp2;
     ctx->have_samp = !sampv.empty(); ctx->samp_nflag = nflag;
     ctx->h_c2fg.assign(c2fg, c2fg + n); ctx->h_r2fg.assign(r2fg, r2fg + n); ctx->h_border.assign(border, border + n);
     ctx->h_c1.assign(c1, c1 + n); ctx->h_r1.assign(r1, r1 + n);
@@ -702,47 +695,18 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         if (!buckets.empty()) { if (int rc = ensure_presampled(ctx, order)) return rc; }
         A.pre = (order >= 2 && !buckets.empty()) ? ctx->pre.p : nullptr;
     }
-    // Launches side by side for SHORT runs.  A full grid is dozens of rounds of workgroups per launch and its launches run one
-    // after the other (side by side they measured 1-6 % slower: a CU that took a workgroup of a large-window class is lost to
-    // several small ones, rounds 2-4).  A rank's shard of an 8-GPU run is two or three launches of one to seven rounds each,
-    // and every launch ends with a half-empty round - a quarter of such a run; side by side the next launch's workgroups fill
-    // the CUs the previous one drains.  Rule: all launches of a run together are at most kSideRounds rounds of workgroups
-    // (side_by_side_rule).  The launches keep their order (largest footprint first).
-    //
-    // LONG runs are CHAINED (pm_plan.h chain_rule): every launch ends with a drain - its last workgroups on a GPU that is
-    // otherwise emptying - and the next launch of the same stream cannot start before the previous one has COMPLETED.  The
-    // starvation above needs workgroups of the earlier launch still waiting to be dispatched, so launch k + 1 is released at
-    // the moment the LAST workgroup of launch k has started (the kernels count their arrival, PMArgs::chain): it fills the
-    // drain slot by slot and competes with nothing.  The launches alternate between side[0] and side[1]; launch k >= 1 is
-    // preceded on its stream by a wait for launch k - 1's release word to reach this run's epoch, and stream order adds
-    // "launch k - 2 has completed": at most two launches in flight.  The handle's stream only forks and joins, as side by
-    // side - the caller's stream, which may be the legacy default stream, never carries a wait.
-    bool side_by_side = false;
-    double rounds = 0;
-    if (buckets.size() > 1) {
-        for (const Bucket &b : buckets) rounds += (double)b.count / (256.0 * launch_shape(b, ctx->rp).round_slots);
-        side_by_side = side_by_side_rule(run_sw, buckets.size(), rounds);
-    }
-    ChainReason chain_why = chain_reason(run_sw, buckets.size(), rounds, ctx->can_wait_value, true);
-    if (chain_why == kChainYes) chain_why = chain_reason(run_sw, buckets.size(), rounds, ctx->can_wait_value, ensure_chain_memory(ctx, buckets.size()));
-    const bool chained = chain_why == kChainYes;
+    // the order of the launches: decided by pm_plan.h launch_schedule (why short runs go side by side and long ones are chained
+    // is told there); the signal memory of a chained run is asked for only when everything else says "chained"
+    Schedule S = launch_schedule(run_sw, buckets, ctx->rp, ctx->can_wait_value, true);
+    if (S.order == Schedule::kChained && !ensure_chain_memory(ctx, buckets.size())) S = launch_schedule(run_sw, buckets, ctx->rp, ctx->can_wait_value, false);
     if (run_sw.verbose) {
+        static const char *const kOrder[] = {"sequence", "side by side", "chained"};
         static const char *const kWhy[] = {"", "", "", "", " (not chained: the device lacks stream wait-value support)", " (not chained: no signal memory)"};
-        fprintf(stderr, "sid_pm: launch order %s, %zu launches%s\n", chained ? "chained" : side_by_side ? "side by side" : "sequence", buckets.size(), kWhy[chain_why]);
+        fprintf(stderr, "sid_pm: launch order %s, %zu launches%s\n", kOrder[S.order], buckets.size(), kWhy[S.why]);
     }
-    // (Switches::side_first, experiments: only the first n launches of a long run side by side - the large-window classes, a
-    // round or two of workgroups each - then the rest in sequence)
-    int n_side = side_by_side ? (int)buckets.size() : 0;
-    if (!side_by_side && run_sw.side_first >= 0) n_side = std::min((int)buckets.size(), run_sw.side_first);
-    if (n_side > 1 || chained) HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
-    int nb = 0;
-    unsigned used = 0;
-    const unsigned long long epoch = chained ? ++ctx->chain_epoch : 0ull;
-    int chain_prev = -1, chain_last = -1;                            // launch index whose release word the next launch waits for; the last launch with points (it releases nobody)
-    if (chained) for (size_t k = 0; k < buckets.size(); ++k) if (buckets[k].count > 0) chain_last = (int)k;
-    // a failure midway: no stream of the handle is left waiting - every release word a wait of this run was enqueued on
-    // gets the epoch from the host (the launch that would have stored it may be the one that failed)
-    auto release_all = [&]() { for (int k = 0; k <= chain_prev; ++k) __atomic_store_n(ctx->chain_release[k], epoch, __ATOMIC_RELEASE); };
+    if (S.record_fork) HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
+    const unsigned long long epoch = S.order == Schedule::kChained ? ++ctx->chain_epoch : 0ull;
+    unsigned used = 0;                                               // side streams that carry work the handle's stream has not joined yet
     auto join = [&]() -> int {
         for (int k = 0; k < 3; ++k)                                  // the handle's stream continues when every side launch is done
             if (used & (1u << k)) {
@@ -752,37 +716,26 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         used = 0;
         return SID_PM_OK;
     };
-    for (const Bucket &b : buckets) {
-        // launch k of a side-by-side run: the handle's stream, then the side streams in turn
-        hipStream_t st = ctx->stream;
-        if (nb == n_side && n_side > 1) { if (int rc = join()) return rc; }
-        if (nb > 0 && nb < n_side) {
-            const int k = (nb - 1) % 3;
-            st = ctx->side[k];
-            if (!(used & (1u << k))) HIP_TRY(hipStreamWaitEvent(st, ctx->fork_ev, 0));
-            used |= 1u << k;
-        }
-        A.chain.count = nullptr; A.chain.release = nullptr; A.chain.epoch = 0;
-        if (chained && b.count > 0) {
-            // launch nb of a chained run: side[0] and side[1] in turn, behind the release of the launch before it; it counts
-            // its arrivals unless it is the last (nobody waits for that one's release word)
-            const int k = nb & 1;
-            st = ctx->side[k];
-            hipError_t e = hipSuccess;
-            if (!(used & (1u << k))) e = hipStreamWaitEvent(st, ctx->fork_ev, 0);
-            used |= 1u << k;
-            if (e == hipSuccess && chain_prev >= 0) e = hipStreamWaitValue64(st, ctx->chain_release[chain_prev], epoch, hipStreamWaitValueGte);
-            if (e != hipSuccess) {
-                release_all();
-                (void)join();
-                return fail(SID_PM_ERR_HIP, "chained launch: stream wait failed: %s", hipGetErrorString(e));
-            }
-            if (nb != chain_last) {
-                A.chain.count = ctx->chain_count + (size_t)nb * sid::kChainWords; A.chain.release = ctx->chain_release[nb]; A.chain.epoch = epoch;
-            }
-        }
-        const int this_launch = nb;
-        ++nb;
+    // a failure midway: no stream of the handle is left waiting (release_upto), and what the side streams already hold still
+    // orders before the handle's stream
+    auto abandon = [&](size_t k, const char *what, hipError_t e) {
+        for (int j = 0; j <= release_upto(S, k); ++j) __atomic_store_n(ctx->chain_release[j], epoch, __ATOMIC_RELEASE);
+        (void)join();
+        return fail(SID_PM_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    for (size_t k = 0; k < buckets.size(); ++k) {
+        const Bucket &b = buckets[k];
+        const LaunchStep &step = S.steps[k];
+        if (step.join_before) { if (int rc = join()) return rc; }
+        const hipStream_t st = step.stream < 0 ? ctx->stream : ctx->side[step.stream];
+        if (step.stream >= 0) used |= 1u << step.stream;
+        hipError_t we = hipSuccess;
+        if (step.wait_fork) we = hipStreamWaitEvent(st, ctx->fork_ev, 0);
+        if (we == hipSuccess && step.wait_release >= 0) we = hipStreamWaitValue64(st, ctx->chain_release[step.wait_release], epoch, hipStreamWaitValueGte);
+        if (we != hipSuccess) return abandon(k, S.order == Schedule::kChained ? "chained launch: stream wait" : "stream wait", we);
+        A.chain.count = step.counts_arrival ? ctx->chain_count + k * sid::kChainWords : nullptr;
+        A.chain.release = step.counts_arrival ? ctx->chain_release[k] : nullptr;
+        A.chain.epoch = step.counts_arrival ? epoch : 0;
         A.order = ctx->d_order + b.offset;
         A.gsii_off = ctx->d_goff.p ? ctx->d_goff.p + b.offset : nullptr;
         A.rec = ctx->d_rec.p ? ctx->d_rec.p + b.offset : nullptr;
@@ -795,12 +748,7 @@ SID_EXPORT int sid_pm_run(sid_pm_ctx *ctx)
         const int e = ctx->rp
                           ? sid::launch_pm_rp(A, lds_launch, nthreads, b.band, b.big ? 0 : ctx->rp_paired, b.pitch, b.occ, st, b.big)
                           : sid::launch_pm_mfma(A, lds_launch, nthreads, b.band, use_paired(ctx->plan.sw, ctx->n_angles), st);
-        if (e != 0) {
-            release_all();
-            (void)join();                                            // (what the side streams already hold still orders before the handle's stream)
-            return fail(SID_PM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        if (A.chain.count) chain_prev = this_launch;                 // (the next launch waits for this one's release word)
+        if (e != 0) return abandon(k, "kernel launch", (hipError_t)e);
     }
     if (int rc = join()) return rc;
     if (int rc = run_large_points(ctx, A)) return rc;
@@ -1025,9 +973,8 @@ SID_EXPORT int sid_pm_get_template(int device, const uint8_t *img, int64_t rows,
     int rc = SID_PM_OK;
     const int64_t nr = std::max<int64_t>(row1 - row0, 0), nc = std::max<int64_t>(col1 - col0, 0);
     if ((rc = dimg.reserve((size_t)std::max<int64_t>(nr * nc, 1))) || (rc = dout.reserve((size_t)s * s)) || (rc = drot.reserve(4)) ||
-        (whole && ((rc = dcoef0.reserve((size_t)(rows * cols))) || (rc = dcoef1.reserve((size_t)(rows * cols)))))) {
-        dimg.release(); dout.release(); drot.release(); dcoef0.release(); dcoef1.release(); return rc;
-    }
+        (whole && ((rc = dcoef0.reserve((size_t)(rows * cols))) || (rc = dcoef1.reserve((size_t)(rows * cols))))))
+        return rc;
     hipError_t e = hipSuccess;
     if (nr > 0 && nc > 0) e = hipMemcpy2D(dimg.p, (size_t)nc, img + row0 * stride + col0, (size_t)stride, (size_t)nc, (size_t)nr, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(drot.p, rot4, sizeof(double) * 4, hipMemcpyHostToDevice);
@@ -1036,7 +983,6 @@ SID_EXPORT int sid_pm_get_template(int device, const uint8_t *img, int64_t rows,
     if (e == hipSuccess) e = (hipError_t)sid::lw_get_template(dimg.p, nc > 0 ? nc : 1, row0, col0, nr, nc, rows, cols, c, r, drot.p, s, rot_order, dout.p, nullptr, whole ? dcoef1.p : nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)s * s, hipMemcpyDeviceToHost);
-    dimg.release(); dout.release(); drot.release(); dcoef0.release(); dcoef1.release();
     if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "get_template: %s", hipGetErrorString(e));
     return SID_PM_OK;
 }
@@ -1053,8 +999,9 @@ SID_EXPORT int sid_pm_get_hessian(int device, const float *ccm, int64_t rows, in
     const size_t n = (size_t)(rows * cols);
     DevBuf<float> din, dout;
     sid::LwWorkspace W;
+    struct Scope { sid::LwWorkspace &w; ~Scope() { sid::lw_workspace_release(w); } } w_scope{W};
     int rc = SID_PM_OK;
-    if ((rc = din.reserve(n)) || (rc = dout.reserve(n))) { din.release(); dout.release(); return rc; }
+    if ((rc = din.reserve(n)) || (rc = dout.reserve(n))) return rc;
     double gw[5];
     gauss_taps(gw);
     hipError_t e = hipMemcpy(din.p, ccm, sizeof(float) * n, hipMemcpyHostToDevice);
@@ -1062,7 +1009,6 @@ SID_EXPORT int sid_pm_get_hessian(int device, const float *ccm, int64_t rows, in
     if (e == hipSuccess) le = sid::lw_get_hessian(din.p, (int)rows, (int)cols, flags, gw, dout.p, W, nullptr);
     if (le == 0 && e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (le == 0 && e == hipSuccess) e = hipMemcpy(hes, dout.p, sizeof(float) * n, hipMemcpyDeviceToHost);
-    din.release(); dout.release(); sid::lw_workspace_release(W);
     if (le == -1) return fail(SID_PM_ERR_NOMEM, "get_hessian: device scratch");
     if (le) return fail(SID_PM_ERR_HIP, "get_hessian: %s", hipGetErrorString((hipError_t)le));
     if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "get_hessian: %s", hipGetErrorString(e));
@@ -1111,14 +1057,12 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
     DevBuf<uint32_t> dgs;                                              // row-pair kernel: this point's sum w'^2 block + its offset (0)
     DevBuf<sid::PointRec> drec;                                        // ... and its record
     int rc = SID_PM_OK;
-    auto cleanup = [&]() { dv.release(); dang.release(); drot.release(); dout.release(); dord.release(); dgs.release(); drec.release();
-                           dij.release(); dshape.release(); dt.release(); dccm.release(); dhes.release(); dcyc.release(); dsamp.release(); dpre.release(); };
     const size_t tcount = (size_t)K * s * s;
     if ((rc = dv.reserve(5)) || (rc = dang.reserve((size_t)K)) || (rc = drot.reserve(4 * (size_t)K)) ||
         (rc = dout.reserve(5)) || (rc = dord.reserve(1)) || (rc = dij.reserve(3)) || (rc = dshape.reserve(2)) ||
         (rc = dt.reserve(tcount)) || (rc = dccm.reserve((size_t)std::max<int64_t>(cap, 1))) ||
         (rc = dhes.reserve((size_t)std::max<int64_t>(cap, 1))) || (rc = dcyc.reserve(32)) ||
-        (rc = dsamp.reserve(sampv.size() + 4)) || (rc = dgs.reserve(64 + (size_t)(wh > s ? sid::rp_block_entries(wh - s + 1, ww - s + 1, rp_rows(rpp, 4), 16 >> rpp, false, keep_acc_policy(sw, rp, rpp, K)) : 64))) || (rc = drec.reserve(1))) { cleanup(); return rc; }
+        (rc = dsamp.reserve(sampv.size() + 4)) || (rc = dgs.reserve(64 + (size_t)(wh > s ? sid::rp_block_entries(wh - s + 1, ww - s + 1, rp_rows(rpp, 4), 16 >> rpp, false, keep_acc_policy(sw, rp, rpp, K)) : 64))) || (rc = drec.reserve(1))) return rc;
     const double v5[5] = {c1, r1, c2fg, r2fg, border};
     const int32_t zero = 0, shape0[2] = {0, 0};
     hipError_t e = hipSuccess;
@@ -1142,8 +1086,7 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
     if (e == hipSuccess) {
         sid::PMArgs A;
         memset(&A, 0, sizeof A);
-        A.img1 = ctx->cur[0].ptr; A.rows1 = ctx->cur[0].rows; A.cols1 = ctx->cur[0].cols; A.stride1 = ctx->cur[0].stride;
-        A.img2 = ctx->cur[1].ptr; A.rows2 = ctx->cur[1].rows; A.cols2 = ctx->cur[1].cols; A.stride2 = ctx->cur[1].stride;
+        set_images(ctx, A);
         A.c1 = dv.p; A.r1 = dv.p + 1; A.c2fg = dv.p + 2; A.r2fg = dv.p + 3; A.border = dv.p + 4;
         A.order = dord.p; A.n_launch = 1; A.img_size = s; A.n_angles = K; A.flags = flags;
         A.angles = dang.p; A.rot = drot.p; A.out = dout.p; A.out_ij = dij.p;
@@ -1154,8 +1097,8 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
         A.lds_bytes = lds;
         const int order = (int)((flags >> 3) & 7u);
         if (order >= 2) {
-            if (int rc2 = ensure_coef(ctx, order)) { cleanup(); return rc2; }
-            if (int rc2 = dpre.reserve(tcount)) { cleanup(); return rc2; }
+            if (int rc2 = ensure_coef(ctx, order)) return rc2;
+            if (int rc2 = dpre.reserve(tcount)) return rc2;
             step((hipError_t)sid::lw_presample(ctx->coef[1].p, ctx->cur[0].rows, ctx->cur[0].cols, dv.p, dv.p + 1, 1, drot.p, K, s, order, dpre.p, ctx->stream));
             A.pre = dpre.p;
         }
@@ -1172,7 +1115,6 @@ SID_EXPORT int sid_pm_debug_point(sid_pm_ctx *ctx, double c1, double r1, double 
         if (ij3) step(hipMemcpy(ij3, dij.p, sizeof(int32_t) * 3, hipMemcpyDeviceToHost));
         if (phase_cycles) step(hipMemcpy(phase_cycles, dcyc.p, sizeof(long long) * 32, hipMemcpyDeviceToHost));
     }
-    cleanup();
     if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "debug_point: %s", hipGetErrorString(e));
     return SID_PM_OK;
 }
@@ -1183,12 +1125,11 @@ SID_EXPORT int sid_pm_debug_rsqrt(sid_pm_ctx *ctx, const double *x, double *y, i
     Guard g(ctx->device);
     DevBuf<double> dx, dy;
     int rc;
-    if ((rc = dx.reserve((size_t)n)) || (rc = dy.reserve((size_t)n))) { dx.release(); dy.release(); return rc; }
+    if ((rc = dx.reserve((size_t)n)) || (rc = dy.reserve((size_t)n))) return rc;
     hipError_t e = hipMemcpy(dx.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = (hipError_t)sid::launch_rsqrt(dx.p, dy.p, n, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(y, dy.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
-    dx.release(); dy.release();
     if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "debug_rsqrt: %s", hipGetErrorString(e));
     return SID_PM_OK;
 }
@@ -1208,7 +1149,6 @@ SID_EXPORT int sid_pm_debug_ncc_selftest(sid_pm_ctx *ctx, uint64_t seed, int64_t
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     unsigned long long h[3] = {0, 0, 0};
     if (e == hipSuccess) e = hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost);
-    d.release();
     if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "debug_ncc_selftest: %s", hipGetErrorString(e));
     for (int k = 0; k < 3; ++k) counts[k] = h[k];
     return SID_PM_OK;
@@ -1228,9 +1168,14 @@ SID_EXPORT int sid_pm_debug_hypot_selftest(sid_pm_ctx *ctx, uint64_t seed, int64
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     unsigned long long h[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost);
-    d.release();
     if (e != hipSuccess) return fail(SID_PM_ERR_HIP, "debug_hypot_selftest: %s", hipGetErrorString(e));
     counts[0] = h[0]; counts[1] = h[1];
+    return SID_PM_OK;
+}
+
+static int check_model_shape(int img_size, int n_angles)
+{
+    if (img_size < 2 || img_size > sid::kLargeMaxSide || n_angles < 1) return fail(SID_PM_ERR_UNSUPPORTED, "img_size / angle count not supported");
     return SID_PM_OK;
 }
 
@@ -1238,7 +1183,7 @@ SID_EXPORT int sid_pm_debug_hypot_selftest(sid_pm_ctx *ctx, uint64_t seed, int64
 static int estimate_checked(const Switches &sw, const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, double *cost_ns, int32_t *per_cu_out)
 {
     if (n < 0 || (n > 0 && (!border || (!cost_ns && !per_cu_out)))) return fail(SID_PM_ERR_ARG, "bad argument");
-    if (img_size < 2 || img_size > sid::kLargeMaxSide || n_angles < 1) return fail(SID_PM_ERR_UNSUPPORTED, "img_size / angle count not supported");
+    if (int rc = check_model_shape(img_size, n_angles)) return rc;
     sid::plan::estimate_points(sw, border, n, img_size, n_angles, flags, cost_ns, per_cu_out);
     return SID_PM_OK;
 }
@@ -1258,43 +1203,13 @@ SID_EXPORT int sid_pm_estimate_residency(const double *border, int64_t n, int im
     return estimate_checked(read_switches(), border, n, img_size, n_angles, flags, nullptr, per_cu);
 }
 
-// Estimated kernel time of ONE run over these points (nanoseconds): per launch class the sum of the point costs plus the tail of
-// the launch - with 256 x (workgroups per CU) points in flight the last round is half empty on average; the classes with few
-// slots run the large borders, whose run times differ by up to 1.5x inside one launch, and end less evenly (fitted to the
-// shards tools/shard_sim.py measures: 1.0 / 0.7 / 0.5 / 0.5 rounds for 1 / 2 / 3 / 4 workgroups per CU) - a launch shorter than
-// one round still takes a full one; a SHORT run (side_by_side_rule, the launcher's own) ends with ONE tail, the longest, and
-// SID_DIST_TAIL_BLEND (0.7) of the others; the points of the large-window pipeline run one after the other behind the launches.
-// LONG runs are priced as a sequence, although the launcher chains them (chain_rule: the next launch fills the previous one's
-// drain): only shards long enough not to be short are affected, rebalance_with_feedback measures those anyway, and the tail
-// constants are refitted once tails under chaining have been measured.
+// the run-time model of pm_plan.h (estimate_run_time) behind the argument checks of the ABI, with the switches of this call
 SID_EXPORT int sid_pm_estimate_run_time(const double *border, int64_t n, int img_size, int n_angles, uint32_t flags, double *time_ns)
 {
     if (!time_ns || n < 0 || (n > 0 && !border)) return fail(SID_PM_ERR_ARG, "bad argument");
     *time_ns = 0.0;
     if (n == 0) return SID_PM_OK;
-    std::vector<double> cost((size_t)n);
-    std::vector<int32_t> cls((size_t)n);
-    const Switches sw = read_switches();
-    if (int rc = estimate_checked(sw, border, n, img_size, n_angles, flags, cost.data(), cls.data())) return rc;
-    struct Part { double sum = 0, count = 0; };
-    Part parts[256];
-    for (int64_t i = 0; i < n; ++i) { Part &p = parts[cls[(size_t)i] & 255]; p.sum += cost[(size_t)i]; p.count += 1; }
-    static const double kTail[5] = {0.5, 1.0, 0.7, 0.5, 0.5};
-    const double blend = sw.tail_blend;
-    double large = 0, sum_all = 0, rounds = 0, tail_max = 0, tail_sum = 0, lat_max = 0, seq = 0;
-    size_t nparts = 0;
-    for (int c = 0; c < 256; ++c) {
-        const Part &p = parts[c];
-        if (p.count == 0) continue;
-        if (c & SID_PM_CLASS_LARGE) { large += p.sum + 150000.0 * ceil(p.count / 64.0); continue; }   // (+ the launches of every batch of 64)
-        const int per_cu = std::max(1, c & SID_PM_CLASS_PER_CU);
-        const double latency = 256.0 * per_cu * (p.sum / p.count), tail = kTail[std::min(per_cu, 4)] * latency;
-        ++nparts; sum_all += p.sum; rounds += p.count / (256.0 * per_cu);
-        tail_max = std::max(tail_max, tail); tail_sum += tail; lat_max = std::max(lat_max, latency);
-        seq += std::max(p.sum + tail, latency);
-    }
-    double t = seq;
-    if (side_by_side_rule(sw, nparts, rounds)) t = std::max(sum_all + tail_max + blend * (tail_sum - tail_max), lat_max);
-    *time_ns = t + large;
+    if (int rc = check_model_shape(img_size, n_angles)) return rc;
+    *time_ns = estimate_run_time(read_switches(), border, n, img_size, n_angles, flags);
     return SID_PM_OK;
 }

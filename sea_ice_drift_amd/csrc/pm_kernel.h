@@ -13,7 +13,7 @@ constexpr uint32_t kSubpixel = 128u;    // SID_PM_SUBPIXEL (include/sid_pm.h), b
 // waits for one memory round trip (launch position -> record) instead of two (position -> index -> five vectors).
 struct PointRec { int32_t pt; uint32_t gsii_off; double c1, r1, c2fg, r2fg, border; };
 
-// Chained launches (sid_pm_run, pm_plan.h chain_rule): every workgroup of a chained launch counts its ARRIVAL first thing in the
+// Chained launches (pm_plan.h launch_schedule / chain_rule): every workgroup of a chained launch counts its ARRIVAL first thing in the
 // kernel, and the one that completes the count releases the stream the next launch waits on - the next launch starts while
 // this one drains, but only once this one has nothing left to dispatch.  The count is sharded (one word takes about 88 adds
 // per microsecond; a launch starts 1024 workgroups in less than one): kChainShards words on 128-byte lines, shard =

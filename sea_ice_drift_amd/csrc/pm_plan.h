@@ -1,7 +1,8 @@
 // pm_plan.h - the launch planner of the pattern-matching core: every decision where host and device must agree (kernel
 // instantiation, window pitch, residency class, band height, block of global memory, free-list policy, launch order), as pure
-// host arithmetic.  No HIP call and no handle: pm_capi.hip turns a Plan into device buffers and launches, tests/cpp/plan_check.cpp
-// checks its invariants with g++ alone, and estimate_points - the cost model the shards are cut with - reads the same functions.
+// host arithmetic.  No HIP call and no handle: pm_capi.hip turns a Plan into device buffers and a Schedule into stream waits and
+// launches, tests/cpp/plan_check.cpp and schedule_check.cpp check their invariants with g++ alone, and estimate_points /
+// estimate_run_time - the cost model the shards are cut with - read the same functions.
 #ifndef SID_PM_PLAN_H
 #define SID_PM_PLAN_H
 
@@ -127,9 +128,9 @@ inline bool window_dims(double c2fg, double r2fg, double border, int s, int64_t 
     return true;
 }
 
-// Launches of a SHORT run go side by side on the handle's side streams (sid_pm_run): all launches of the run together are at most
-// kSideRounds rounds of workgroups.  ONE rule for the launcher and for the estimate the shard cuts are made with
-// (sid_pm_estimate_run_time).
+// Launches of a SHORT run go side by side on the handle's side streams (launch_schedule): all launches of the run together are at
+// most kSideRounds rounds of workgroups.  ONE rule for the launcher and for the estimate the shard cuts are made with
+// (estimate_run_time); each counts its rounds in its own way, see there.
 constexpr double kSideRounds = 16.0;
 inline bool side_by_side_rule(const Switches &sw, size_t n_launches, double rounds)
 {
@@ -137,7 +138,7 @@ inline bool side_by_side_rule(const Switches &sw, size_t n_launches, double roun
     return sw.side_by_side >= 0 ? sw.side_by_side > 0 : rounds <= kSideRounds;
 }
 
-// Launches of a LONG run are CHAINED (sid_pm_run): launch k + 1 is released when the last workgroup of launch k has STARTED
+// Launches of a LONG run are CHAINED (launch_schedule): launch k + 1 is released when the last workgroup of launch k has STARTED
 // (the kernels count their arrival: PMArgs::chain), so it fills the CUs launch k drains and never competes with workgroups
 // of launch k that still wait to be dispatched - what made whole launches side by side slower.  The release is a stream wait
 // on signal memory, a beta interface of the runtime: the device must report it (hipDeviceAttributeCanUseStreamWaitValue)
@@ -297,7 +298,7 @@ struct Bucket {
     bool pooled = false;            // the launch takes its blocks of global memory from the free lists (PMArgs::ring)
 };
 
-// Workgroups per CU and threads per point of a launch, for the launch loop and the round count of sid_pm_run.
+// Workgroups per CU and threads per point of a launch, for the launch loop of sid_pm_run and the round count of launch_schedule.
 // per_cu: the workgroups a CU holds - what the LDS footprint allows, capped by the kernel build (two wavefronts per SIMD for the
 // 8-row band; 3, or 4 for the 128-VGPR build and for the three-wavefront class): the class the cost model reports.
 // round_slots: per_cu WITHOUT the cap of the build (4 wherever the LDS fits four times): the round count of side_by_side_rule
@@ -314,6 +315,83 @@ inline LaunchShape launch_shape(const Bucket &b, bool rp)
     const int fit = std::max(1, blocks_per_cu(b.lds));
     const int per_cu = std::min(b.band == 8 ? 2 : (b.occ == 4 || w3) ? 4 : kMaxPerCu, fit);
     return LaunchShape{per_cu, std::min(b.band == 8 ? 2 : 4, fit), b.band == 8 ? 256 : (fit == 1 ? 768 : w3 ? 192 : 256)};
+}
+
+// The order in which a run puts its launches onto streams, decided here and only executed by sid_pm_run.
+//
+// Launches side by side for SHORT runs.  A full grid is dozens of rounds of workgroups per launch and its launches run one
+// after the other (side by side they measured 1-6 % slower: a CU that took a workgroup of a large-window class is lost to
+// several small ones, rounds 2-4).  A rank's shard of an 8-GPU run is two or three launches of one to seven rounds each,
+// and every launch ends with a half-empty round - a quarter of such a run; side by side the next launch's workgroups fill
+// the CUs the previous one drains.  Rule: all launches of a run together are at most kSideRounds rounds of workgroups
+// (side_by_side_rule).  The launches keep their order (largest footprint first): launch 0 on the handle's stream, launch k on
+// side[(k - 1) % 3], and the handle's stream continues when every side stream is done (the join).
+// (Switches::side_first, experiments: only the first n launches of a long run side by side - the large-window classes, a
+// round or two of workgroups each - then the join and the rest in sequence.  The order is still reported as a sequence.)
+//
+// LONG runs are CHAINED (chain_rule): every launch ends with a drain - its last workgroups on a GPU that is otherwise
+// emptying - and the next launch of the same stream cannot start before the previous one has COMPLETED.  The starvation
+// above needs workgroups of the earlier launch still waiting to be dispatched, so launch k + 1 is released at the moment the
+// LAST workgroup of launch k has started (the kernels count their arrival, PMArgs::chain): it fills the drain slot by slot
+// and competes with nothing.  The launches alternate between side[0] and side[1]; launch k >= 1 is preceded on its stream
+// by a wait for the release word of the launch before it to reach this run's epoch, and stream order adds "launch k - 2 has
+// completed": at most two launches in flight.  The last launch counts nothing: nobody waits for its release word.  The
+// handle's stream only forks and joins, as side by side - the caller's stream, which may be the legacy default stream, never
+// carries a wait.  (A launch without points - the planner makes none - is a plain step on the handle's stream.)
+struct LaunchStep {
+    int stream = -1;                // -1: the handle's stream; 0..2: side[k]
+    bool join_before = false;       // the handle's stream first waits for the side streams used so far
+    bool wait_fork = false;         // first use of that side stream in this run: it waits for the fork event
+    int wait_release = -1;          // chained: launch index whose release word this launch waits for (-1: none)
+    bool counts_arrival = false;    // chained: PMArgs::chain is set - the launch's last-arriving workgroup stores its release word
+};
+struct Schedule {
+    enum Order { kSequence = 0, kSideBySide, kChained };
+    Order order = kSequence;
+    ChainReason why = kChainSingle;
+    bool record_fork = false;       // some step waits for the fork event
+    // rounds of workgroups of the run, each launch at the slots its LDS footprint allows (LaunchShape::round_slots, not capped by the
+    // kernel build): kSideRounds was fitted with this count, while estimate_run_time counts at the capped per_cu its tails were fitted with
+    double rounds = 0;
+    std::vector<LaunchStep> steps;  // one per bucket, in bucket order
+};
+inline Schedule launch_schedule(const Switches &run_sw, const std::vector<Bucket> &buckets, bool rp, bool can_wait_value, bool have_signal_memory)
+{
+    Schedule S;
+    const size_t n = buckets.size();
+    for (const Bucket &b : buckets) S.rounds += (double)b.count / (256.0 * launch_shape(b, rp).round_slots);
+    const bool side_by_side = side_by_side_rule(run_sw, n, S.rounds);
+    S.why = chain_reason(run_sw, n, S.rounds, can_wait_value, have_signal_memory);
+    const bool chained = S.why == kChainYes;
+    S.order = chained ? Schedule::kChained : side_by_side ? Schedule::kSideBySide : Schedule::kSequence;
+    const size_t n_side = side_by_side ? n : run_sw.side_first >= 0 ? std::min(n, (size_t)run_sw.side_first) : 0;
+    int last = -1, counting = -1;                                     // chained: the last launch with points; the latest launch so far that counts its arrivals
+    if (chained) for (size_t k = 0; k < n; ++k) if (buckets[k].count > 0) last = (int)k;
+    unsigned used = 0;
+    S.steps.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+        LaunchStep &st = S.steps[k];
+        st.join_before = k == n_side && n_side > 1;
+        int side = (k > 0 && k < n_side) ? (int)((k - 1) % 3) : -1;
+        if (chained && buckets[k].count > 0) {
+            side = (int)(k & 1);
+            st.wait_release = counting;
+            st.counts_arrival = (int)k != last;
+            if (st.counts_arrival) counting = (int)k;
+        }
+        if (side >= 0) { st.stream = side; st.wait_fork = !(used & (1u << side)); used |= 1u << side; }
+    }
+    S.record_fork = used != 0;                                        // (= more than one launch side by side, or chained - with a launch that has points)
+    return S;
+}
+// A failure at step k (its wait or its launch) must leave no stream waiting: the release words 0 .. this index get the epoch from
+// the host - every word a wait was enqueued on up to and including step k (the launch that would have stored it may be the one
+// that failed).  -1: none.
+inline int release_upto(const Schedule &S, size_t k)
+{
+    int upto = -1;
+    for (size_t j = 0; j <= k && j < S.steps.size(); ++j) upto = std::max(upto, S.steps[j].wait_release);
+    return upto;
 }
 
 // What a plan is made from: the resident points (host copies), the sweep, the shape of the current pair, and the kernel
@@ -728,6 +806,45 @@ inline void estimate_points(const Switches &sw, const double *border, int64_t n,
         if (cost_ns) cost_ns[i] = (kSweep * sweep + kWinner * winner + kPos * (double)r * r + kFixed) * cls_factor;
         if (per_cu_out) per_cu_out[i] = cls;
     }
+}
+
+// Estimated kernel time of ONE run over these points (nanoseconds): per launch class the sum of the point costs plus the tail of
+// the launch - with 256 x (workgroups per CU) points in flight the last round is half empty on average; the classes with few
+// slots run the large borders, whose run times differ by up to 1.5x inside one launch, and end less evenly (fitted to the
+// shards tools/shard_sim.py measures: 1.0 / 0.7 / 0.5 / 0.5 rounds for 1 / 2 / 3 / 4 workgroups per CU) - a launch shorter than
+// one round still takes a full one; a SHORT run (side_by_side_rule, the launcher's own) ends with ONE tail, the longest, and
+// Switches::tail_blend (0.7) of the others; the points of the large-window pipeline run one after the other behind the launches.
+// LONG runs are priced as a sequence, although the launcher chains them (chain_rule: the next launch fills the previous one's
+// drain): only shards long enough not to be short are affected, rebalance_with_feedback measures those anyway, and the tail
+// constants are refitted once tails under chaining have been measured.
+inline double estimate_run_time(const Switches &sw, const double *border, int64_t n, int s, int K, uint32_t flags)
+{
+    if (n <= 0) return 0.0;
+    std::vector<double> cost((size_t)n);
+    std::vector<int32_t> cls((size_t)n);
+    estimate_points(sw, border, n, s, K, flags, cost.data(), cls.data());
+    struct Part { double sum = 0, count = 0; };
+    Part parts[256];
+    for (int64_t i = 0; i < n; ++i) { Part &p = parts[cls[(size_t)i] & 255]; p.sum += cost[(size_t)i]; p.count += 1; }
+    static const double kTail[5] = {0.5, 1.0, 0.7, 0.5, 0.5};
+    const double blend = sw.tail_blend;
+    double large = 0, sum_all = 0, rounds = 0, tail_max = 0, tail_sum = 0, lat_max = 0, seq = 0;
+    size_t nparts = 0;
+    for (int c = 0; c < 256; ++c) {
+        const Part &p = parts[c];
+        if (p.count == 0) continue;
+        if (c & SID_PM_CLASS_LARGE) { large += p.sum + 150000.0 * ceil(p.count / 64.0); continue; }   // (+ the launches of every batch of 64)
+        const int per_cu = std::max(1, c & SID_PM_CLASS_PER_CU);
+        const double latency = 256.0 * per_cu * (p.sum / p.count), tail = kTail[std::min(per_cu, 4)] * latency;
+        // rounds of workgroups at the workgroups per CU the class REPORTS (capped by the kernel build); launch_schedule counts the slots
+        // the LDS footprint allows (LaunchShape::round_slots, up to 4): the tail constants above were fitted with this count, the launcher's rule with that
+        ++nparts; sum_all += p.sum; rounds += p.count / (256.0 * per_cu);
+        tail_max = std::max(tail_max, tail); tail_sum += tail; lat_max = std::max(lat_max, latency);
+        seq += std::max(p.sum + tail, latency);
+    }
+    double t = seq;
+    if (side_by_side_rule(sw, nparts, rounds)) t = std::max(sum_all + tail_max + blend * (tail_sum - tail_max), lat_max);
+    return t + large;
 }
 
 }  // namespace plan

@@ -1,0 +1,73 @@
+// Host-side check of the run-time model (sea_ice_drift_amd/csrc/pm_plan.h estimate_run_time): compiled and run by
+// tests/test_schedule_host.py with g++ alone.  Arguments: tests/golden/run_time_cases.txt - what sid_pm_estimate_run_time of the
+// library answered before the model moved into pm_plan.h (tools/record_run_time_cases.py tells the format) - and a file with the
+// border vector of the benchmark grid (count, then the values).  Every case is recomputed from pm_plan.h alone and the doubles
+// must be EQUAL.  One line per violation, then "<n> violations".
+#include <cstdio>
+#include <cstdint>
+#include <fstream>
+#include <sstream>
+#define __host__
+#define __device__
+#include "../../sea_ice_drift_amd/csrc/pm_plan.h"
+
+// what the kernels' translation unit answers, mirrored for a build without HIP (as in plan_check.cpp)
+namespace sid {
+int max_lds_bytes() { return 160 * 1024; }
+bool mfma_img_size_supported(int s) { return s >= 2 && s <= 64; }
+bool mfma_band8_supported(int s) { return s == 34 || s == 35; }
+bool rp_pitch_instantiated(int band, int paired, int pitch, int occ)
+{
+    if (occ == 4) return band == 4 && (pitch == 104 || pitch == 112) && (paired == 1 || paired == 2);
+    const bool common = pitch == 136 || pitch == 168 || pitch == 0;
+    if (paired == 0 && band == 8) return common;
+    return common || pitch == 104 || pitch == 112 || pitch == 1104;
+}
+}  // namespace sid
+
+using namespace sid::plan;
+
+int main(int argc, char **argv)
+{
+    if (argc < 3) { printf("usage: run_time_check CASES GRID_BORDERS\n1 violations\n"); return 2; }
+    std::vector<double> grid;
+    {
+        std::ifstream g(argv[2]);
+        size_t n = 0;
+        g >> n;
+        grid.resize(n);
+        for (double &v : grid) g >> v;
+        if (g.fail()) grid.clear();
+    }
+    std::ifstream f(argv[1]);
+    std::string line;
+    int bad = 0, cases = 0;
+    static const int kAngles[4] = {3, 7, 15, 16}, kSide[3] = {-1, 0, 1};
+    static const unsigned kFlags[2] = {1, 7};
+    static const double kBlend[2] = {Switches().tail_blend, atof("0.3")};   // (unset; as read_switches reads "0.3")
+    while (std::getline(f, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream in(line);
+        std::string borders, word;
+        int s = 0;
+        in >> borders >> s;
+        std::vector<double> constant;
+        if (borders != "grid") constant.assign((size_t)atol(borders.c_str() + borders.find(':') + 1), atof(borders.c_str()));
+        const std::vector<double> &b = borders == "grid" ? grid : constant;
+        double want = 0;
+        for (int K : kAngles) for (unsigned flags : kFlags) for (int side : kSide) for (double blend : kBlend) {
+            in >> word;
+            if (word != "=") want = strtod(word.c_str(), nullptr);
+            Switches sw;
+            sw.side_by_side = side; sw.tail_blend = blend;
+            const double got = estimate_run_time(sw, b.data(), (int64_t)b.size(), s, K, flags);
+            ++cases;
+            if (!(got == want) || in.fail() || b.empty()) {
+                if (++bad < 40) printf("%s img_size %d, %d angles, flags %u, side by side %d, blend %g: recorded %.17g, pm_plan.h %.17g\n", borders.c_str(), s, K, flags, side, blend, want, got);
+            }
+        }
+    }
+    if (cases != 5952 || grid.size() != 40000) { ++bad; printf("%d cases, %zu grid points: the list is 5952 cases, the grid 40000 points\n", cases, grid.size()); }
+    printf("%d cases\n%d violations\n", cases, bad);
+    return bad ? 1 : 0;
+}

@@ -1,4 +1,4 @@
-"""Chained launches (csrc/pm_capi.hip sid_pm_run, csrc/pm_plan.h chain_rule): the launches of a long run
+"""Chained launches (csrc/pm_plan.h launch_schedule / chain_rule, executed by sid_pm_run): the launches of a long run
 go alternately onto two side streams, and launch k + 1 is released - a stream wait on signal memory - by the workgroup of
 launch k that arrives last (PMArgs::chain).  Nothing in the results may depend on that order, so every case compares a chained
 run bit for bit, NaN rows included, with the same run under SID_PM_NO_CHAIN=1, and with the C oracle under the parity rule
