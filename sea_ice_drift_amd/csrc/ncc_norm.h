@@ -1,5 +1,5 @@
 // Normalisation of the winner's NCC matrix: the specification's route and the shortened one, as plain arithmetic that the
-// kernels (pm_kernel_mfma.hip, pm_kernel_rp.inc) and the host check (tests/cpp/ncc_norm_check.cpp) both compile.
+// kernels (through pm_kernel_base.h) and the host check (tests/cpp/ncc_norm_check.cpp) both compile.
 // Everything here counts IEEE roundings: build with -ffp-contract=off; the fused operations are written out as __builtin_fma.
 //
 // Inputs of one placement (all integers, re-centred int8 domain w' = w - 128, t' = t - 128 ... see DESIGN.md section 3):

@@ -1,7 +1,8 @@
-// Shared between the HIP kernel (pm_kernel_mfma.hip) and the host C-ABI (pm_capi.hip).
+// Shared between the HIP kernels (pm_kernel_mfma.hip, pm_kernel_rp_occ4.hip) and the host C-ABI (pm_capi.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "pm_instances.h"   // the kernels' instantiations; max_lds_bytes, mfma_*_supported, rp_pitch_instantiated
 
 namespace sid {
 
@@ -131,7 +132,7 @@ __host__ __device__ inline void subpixel_offsets(const float *R, int rh, int rw,
     dy = (iy > 0 && iy < rh - 1) ? subpixel_fit(p[-rw], p[0], p[rw]) : 0.0;
 }
 
-// ---- MFMA kernel (pm_kernel_mfma.hip) ----
+// ---- MFMA kernel (pm_kernel_classic.h) ----
 constexpr int kMiscMfmaBytes = 2688;
 constexpr int kTrowPad = 36;         // zero rows around a winner operand block: 16 above, 20 below (the step loop runs in fours)
 constexpr int kQueueCap = 192;       // arg-max candidates waiting for exact evaluation (16 B each)
@@ -408,12 +409,8 @@ struct RpSweepItems {
 };
 // ragged_ok (rp_sweep_ragged_ok): the full-table kernels without kept accumulators (slot groups map slots 8..15 to other
 // rows, and a kept accumulator table is padded to whole items of ONE band: they keep today's tiling)
-// (paired: 0 = full table, 1 / 2 = slot groups; -DSID_KEEP_ACC_FULL compiles kept accumulators into the full-table kernels too)
-#ifdef SID_KEEP_ACC_FULL
-__host__ __device__ constexpr bool rp_sweep_ragged_ok(int) { return false; }
-#else
+// (paired: 0 = full table, 1 / 2 = slot groups; tools/patches/keep_acc_full.patch compiled kept accumulators into the full-table kernels too)
 __host__ __device__ constexpr bool rp_sweep_ragged_ok(int paired) { return paired == 0; }
-#endif
 __host__ __device__ inline RpSweepItems rp_sweep_items(int rh, int rw, int rows, bool ragged_ok)
 {
     RpSweepItems I;
@@ -500,14 +497,8 @@ __host__ __device__ inline int rp_class_pitch(int natural)
 }
 // paired: 0 = one group of 16 slots, 1 = two groups (at most 7 angles), 2 = four groups (at most 3 angles)
 // occ: wavefronts per SIMD the build allows - 3, or 4 (128 VGPRs; slot groups with pitch 104 only: four workgroups per CU)
-// kept accumulators are compiled into the slot-group kernels (paired != 0); into all with -DSID_KEEP_ACC_FULL (pm_kernel_rp.inc)
-#ifdef SID_KEEP_ACC_FULL
-constexpr bool kKeepAccFull = true;
-#else
-constexpr bool kKeepAccFull = false;
-#endif
+// kept accumulators are compiled into the slot-group kernels only (paired != 0; pm_kernel_rp.inc)
 int launch_pm_rp(const PMArgs &args, int lds_bytes, int nthreads, int band, int paired, int pitch, int occ, void *stream, bool big = false);
-bool rp_pitch_instantiated(int band, int paired, int pitch, int occ = 3);
 
 __host__ __device__ inline int samp_pitch(int s) { return round_up(s, 4); }
 constexpr int kSamp2Cap = 320;                                              // units per angle: 35 rows x 9 quads = 315
@@ -517,12 +508,9 @@ constexpr double kSampGuard = 1e-5;   // table entries whose coordinate is this 
 int launch_pm_mfma(const PMArgs &args, int lds_bytes, int nthreads, int band, bool paired, void *stream);
 constexpr int kPairedMaxAngles = 7;   // angle sets this small run the paired sweep
 constexpr int kQuadMaxAngles = 3;     // ... and these four slot groups (row-pair kernel)
-bool mfma_band8_supported(int s);
-bool mfma_img_size_supported(int s);
 
 int launch_rsqrt(const double *x, double *y, int64_t n, void *stream);
 int launch_ncc_selftest(unsigned long long seed, int blocks, int per_thread, int s, unsigned long long *out, void *stream);
 int launch_hypot_selftest(unsigned long long seed, int blocks, int per_thread, unsigned long long *out, void *stream);
-int max_lds_bytes();
 
 }  // namespace sid

@@ -1,5 +1,7 @@
-// pm_kernel_rp.inc - the "row-pair" sweep for template sides 34 and 35 (included by pm_kernel_mfma.hip inside
-// its anonymous namespace; shares the window / sums / patch / winner / Hessian phases with the classic kernel).
+// pm_kernel_rp.inc - the "row-pair" kernel for template sides 34 and 35: pm_kernel_rp<S, BAND, PAIRED, PITCH, BIG> and its own
+// sums, operand, sweep and winner phases.  Needs pm_kernel_phases.h (the window / patch / Hessian phases, the sampler's helpers and
+// the five-dword window fragment it shares with the classic kernel) and, through it, SID_PM_OCC.  Included by pm_kernel_mfma.hip
+// (three wavefronts per SIMD) and pm_kernel_rp_occ4.hip (four).
 //
 // Why: the classic sweep multiplies one template row per MFMA - K = 64 window columns for a 34-column row, 47 %
 // zeros - builds every window fragment from five ds_read_b32 (LDS-bound: 29 cycles per MFMA instead of 16) and
@@ -34,6 +36,13 @@
 // matrix of the winning angle has a row-pair form of its own (rp_winner).  The integers are the same everywhere, so
 // the results are bit-identical.
 
+#pragma once
+#include "pm_kernel_phases.h"
+
+namespace sid {
+
+namespace {
+
 // Wave priorities by phase (s_setprio).  The short phases between the barriers of a workgroup are latency chains; the sweep
 // is throughput work that can fill whatever issue slots the other workgroups of the CU leave.  With the phases before the
 // sweep and the arg-max at priority 3, the Hessian at 2, the winner's matrix at 1 and the sweep at 0 the 15-angle step is
@@ -66,13 +75,8 @@
     if (PAIRED != 0 && ((SID_Q_PRE) | (SID_Q_SWEEP) | (SID_Q_POST) | (SID_Q_WIN) | (SID_Q_HES))) __builtin_amdgcn_s_setprio(SID_Q_##phase); } while (0)
 
 // Kept accumulators (PMArgs::gs_keep_acc) are compiled into the slot-group kernels only: the full-table kernels would carry the
-// stores and the second winner through their 168 registers for a launch flag that is off by default.  -DSID_KEEP_ACC_FULL
-// (measurement builds, SID_PM_KEEP_ACC=1) compiles them into every gs instantiation.
-#ifdef SID_KEEP_ACC_FULL
-#define SID_KEEP_ACC_OK(PAIRED) true
-#else
-#define SID_KEEP_ACC_OK(PAIRED) ((PAIRED) != 0)
-#endif
+// stores and the second winner through their 168 registers for a launch flag that is off by default
+// (tools/patches/keep_acc_full.patch compiled them into every gs instantiation: +12 %, DESIGN.md section 5.2).
 
 struct Raw6 { u32 d[6]; };
 // 24 bytes at an 8-aligned LDS offset as three ds_read_b64.  The three offsets (o, o + 8, o + 16) are kept in
@@ -295,12 +299,8 @@ __device__ __forceinline__ void rp_sums_cols(const u32 *rowsum, u32 *gs, int rh,
 }
 
 // wavefront-instructions of a pass: whole wavefronts of tasks x instructions per task (static counts of the task bodies)
-#ifdef SID_SUMS_BY_ROUNDS
-// (A/B builds: the longest chain of a thread instead - rounds of the workgroup x instructions per task)
-#define SID_SUMS_GROUPS(tasks) (((tasks) + kBlockM - 1) / kBlockM)
-#else
+// (the other rule - the longest chain of a thread - is tools/patches/sums_by_rounds.patch)
 #define SID_SUMS_GROUPS(tasks) (((tasks) + 63) >> 6)
-#endif
 __device__ __forceinline__ int rp_sums_row_cost(int wh, int rw, int seg) { return SID_SUMS_GROUPS(wh * ((rw + seg - 1) / seg)) * (5 * seg + 24); }
 __device__ __forceinline__ int rp_sums_col_cost(int rh, int rw, int s, int segr)
 {
@@ -547,13 +547,8 @@ __device__ __noinline__ void rp_tpl_general(int a0, int Kg, long long rows1, lon
         for (int k0 = 0; k0 * g.ngrp < s; k0 += kRowsPerThread) {
             for (int aa = 0; aa < Kg; ++aa) {
                 int st = 0, stt = 0;
-#ifdef SID_DBG_EXACT
-                u32 db = 0;
-                for (int u = 0; u < kRowsPerThread; ++u) db |= (g.act && g.ig + (k0 + u) * g.ngrp < s) ? (1u << u) : 0u;
-#else
                 const u32 db = sample_fast5<INSIDE>(g, m->rot[aa], true, k0, st, stt, sawzero,
                     [&](int, int i, int v, bool take) { if (take) smem[rp_off<TS>(G, i, g.j, aa)] = (uint8_t)(v ^ 0x80); });
-#endif
                 // the doubtful samples (coordinate within kGuard of a rounding or image boundary): scipy's double arithmetic
                 for (int u = 0; u < kRowsPerThread; ++u) {
                     if ((db >> u) & 1u) {
@@ -691,13 +686,9 @@ __device__ __forceinline__ void rp_item_main(v4i (&acc)[BAND][PAIR ? 2 : 1], con
     struct Frag { v4i f[NT]; };
     struct RawT { Raw6 p; Raw5 q; };
     Off3 b3 = Off3::make(bo);
-#ifdef SID_SINGLE_READ2
-    auto rd = [&](u32 d) { RawT r; if (PAIR) r.p = read_raw6(b3.plus(d)); else r.q = read_raw(smem + bo + d); return r; };
-#else
     constexpr bool kB32 = !PAIR && rp_pitch_bytes(PITCH) != 0;         // (compile-time pitch: the offsets are immediates)
     Off5 b5 = Off5::make(kB32 ? bo : 0u);
     auto rd = [&](u32 d) { RawT r; if (PAIR) r.p = read_raw6(b3.plus(d)); else if (kB32) r.q = read_raw5(b5, d); else r.q = read_raw(smem + bo + d); return r; };
-#endif
     auto build = [&](const RawT &r) {
         Frag o;
         if (PAIR) { o.f[0] = align_raw6<0>(r.p, sh); o.f[NT - 1] = align_raw6<1>(r.p, sh); }
@@ -847,7 +838,7 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
     int *si_tab = GSW ? reinterpret_cast<int *>(const_cast<u32 *>(sii) + G.gsi) : reinterpret_cast<int *>(smem + G.si_off);
     // kept accumulators (PMArgs::gs_keep_acc; gs launches): every lane stores its four slots of every (row, placement) it holds
     // - 16 bytes each - for rp_winner_kept
-    constexpr bool KEEPC = GSW && SID_KEEP_ACC_OK(PAIRED);
+    constexpr bool KEEPC = GSW && PAIRED != 0;
     const int gsa = KEEPC ? __builtin_amdgcn_readfirstlane(G.gsa) : 0, gsa_rw = KEEPC ? __builtin_amdgcn_readfirstlane(G.gsa_rw) : 0;
     const float maxA = __builtin_amdgcn_readfirstlane(__float_as_int(m->maxA)) == 0 ? 0.0f
                      : __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m->maxA)));
@@ -999,16 +990,6 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
             const float gm = key2f(gkey);
             sc.lmax = gm > sc.lmax ? gm : sc.lmax;
         }
-#ifdef SID_ABLATE_SCORE
-        {   // measurement builds only: keep the MFMAs alive, skip the scoring
-            int x = 0;
-#pragma unroll
-            for (int t = 0; t < BAND; ++t) x ^= accA[t][0] ^ accA[t][1] ^ accA[t][2] ^ accA[t][3] ^ accB[t][0] ^ accB[t][1] ^ accB[t][2] ^ accB[t][3];
-            sc.bestv = 0.5f; sc.bestkey = 17;
-            if (x == 0x12345678) m->red_i[3] = (int)siis[0][0] + (int)okbits;
-            continue;
-        }
-#endif
         // ---- scoring, pass A (always, branch-free): float32 estimates, their maximum per output row and per lane ----
         int swp[2][BAND]; float rIf[2][BAND], rowv[2][BAND];
         float itemmax = -INFINITY;
@@ -1024,11 +1005,7 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
                 const v4i (&acc)[BAND] = k == 0 ? accA : accB;
 #pragma unroll
                 for (int t = 0; t < BAND; ++t)                         // the ones slot = sum of w': slot 15 (lanes 48..63, register 3)
-#ifdef SID_ABL_NO_SWP
-                    swp[k][t] = acc[t][3];
-#else
                     swp[k][t] = PAIRED == 2 ? acc[t][3] : __builtin_amdgcn_ds_bpermute(sw_src, acc[t][3]);
-#endif
                 // this lane's share of the per-placement terms
                 float ris[NSH];
 #pragma unroll
@@ -1048,13 +1025,9 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
                     // (where the residency class has room: sum w' of the placement kept for the winner's matrix, rp_lds_layout)
                     if (keep_si && ((okbits >> (BAND * k + tj)) & 1u))
                         sii_put(reinterpret_cast<u32 *>(si_tab), pidx(k, tj), (u32)sw);
-#ifdef SID_ABL_NO_RI
-                    float ri = __int_as_float(0x3a000000 + (sw & 0xff) + (int)(siis[k][j] & 0xff));
-#else
                     const double swd = (double)sw, siid = (double)siis[k][j];
                     const double dI = nd * siid - swd * swd;          // exact
                     float ri = __builtin_amdgcn_rsqf((float)dI);
-#endif
                     // (nearly) flat window or template - also every dI <= N / 2 of the spec's low-variance rule, since
                     // N / sqrt(dT) >= 1 / 128: the float32 estimate is not trusted, the exact path decides
                     const bool flat = !(ri * maxA <= kGuardA);
@@ -1064,19 +1037,10 @@ __device__ __forceinline__ Score rp_sweep(Score sc, int a0, int Kg, const u32 *s
                 }
 #pragma unroll
                 for (int t = 0; t < BAND; ++t)
-#ifdef SID_ABL_NO_RI
-                    rIf[k][t] = ris[j_of(t)];
-#else
                     rIf[k][t] = PAIRED == 2 ? ris[j_of(t)] : __int_as_float(__builtin_amdgcn_ds_bpermute(src_of(t), __float_as_int(ris[j_of(t)])));
-#endif
 #pragma unroll
                 for (int t = 0; t < BAND; ++t) {
                     const float ri = rIf[k][t];                       // NaN for a flat window
-#ifdef SID_ABL_NO_P4
-                    { const bool ok = (okbits >> (BAND * k + t)) & 1u;
-                      const float rv = ok ? (float)(acc[t][0] ^ acc[t][1] ^ acc[t][2] ^ acc[t][3] ^ swp[k][t]) * ri * 1e-12f : -INFINITY;
-                      rowv[k][t] = rv; itemmax = fmaxf(itemmax, rv); continue; }
-#endif
                     const float swf = (float)swp[k][t];
                     // exact acc - m Sw' (v_mad_i32_i24), then two packed float32 FMAs per pair of slots
                     v2f ai01, ai23;
@@ -1237,26 +1201,8 @@ constexpr int kWPad = 16, kWRows = 68;                                 // 16 + s
 constexpr int kTrOff = 0, kTr1Off = kWRows * 32, kTsOff = 2 * kWRows * 32, kTs1Off = 2 * kWRows * 32 + kWRows * 16;
 static_assert(kTs1Off + kWRows * 16 <= 8192, "winner operands exceed their 8 KB");
 
-// Round 5, "x-shift" form of the winner's matrix (rp_winx_*; -DSID_WINNER_X; the default is the output-row form above):
-//   M = 16 x-SHIFTS of ONE template row, N = 16 output ROWS, K = 64 window columns of one window row:
-//   A[m][k] = T'[i][k - m]  (zero outside the template),   B[k][n] = W'[y0 + n + i][x0 + k],   D[m][n] += A B over the s rows i
-//   = S_IT' of placement (y0 + n, x0 + m).  x0 and y0 are multiples of 16, so a lane's B fragment - 16 bytes of window row
-//   y0 + n + i at column x0 + 16 g - is two ALIGNED ds_read_b64: no v_alignbyte at all on the window side (the row form builds
-//   every window fragment from three ds_read_b64 + 8 v_alignbyte per two matrix instructions).  The A fragment - template row i
-//   shifted by the lane's m - is built once per row (5 dwords + 4 v_alignbyte) and shared by all tiles of a pass.
-//   s (34 | 35) matrix instructions per 16 x 16 placements: 306 for a 42 x 42 matrix (342 in the row form).
-// Operands: template rows padded to kXRow bytes, T'[i][c] at byte kXPad + c of row i; an all-ones row (kXOnesRow) for sum w'.
-constexpr int kXRow = 96, kXPad = 16, kXOnesRow = 36;
-static_assert((kXOnesRow + 1) * kXRow <= 8192, "x-shift winner operands exceed their 8 KB");
-// Measured (profiles/r05_ab_winner_x_shift.txt, same box, kernel ms per 40 000 points): border 20 -0.4 %, mixed +-0, border 26
-// +4 %, border 30 +2.6 %, border 50 +1.5 %, 7 angles at border 30 +5 % - the 16-row tiles of this form fit the residency classes
-// of the larger windows worse than the pair tiles (a pass of three tiles per wavefront leaves wavefronts idle), and its gs
-// instantiations spill 3-10 registers.  Bit-exact on every parity test; compiled with -DSID_WINNER_X only.
-#ifdef SID_WINNER_X
-constexpr bool kWinX = true;
-#else
-constexpr bool kWinX = false;
-#endif
+// (Round 5 also measured an "x-shift" form of this matrix - M = 16 x-shifts of one template row, aligned window fragments, 306
+// matrix instructions instead of 342 -: no faster, tools/patches/winner_x.patch)
 
 template <int S>
 __device__ __noinline__ void rp_winner_stage(const double *rot4, const uint16_t *samp, long long rows1, long long cols1, int ka)
@@ -1270,11 +1216,9 @@ __device__ __noinline__ void rp_winner_stage(const double *rot4, const uint16_t 
     __syncthreads();
     const SampleGeom g = sample_geom(G, s, rows1, cols1, patch);
     auto put = [&](int i, int j, int v) {
-        if (kWinX) { base[i * kXRow + kXPad + j] = (uint8_t)(v ^ 0x80); return; }
         if (j < 32) { base[kTrOff + (i + kWPad) * 32 + j] = (uint8_t)(v ^ 0x80); base[kTr1Off + (i + kWPad) * 32 + j] = 1; }
         else { base[kTsOff + (i + kWPad) * 16 + (j - 32)] = (uint8_t)(v ^ 0x80); base[kTs1Off + (i + kWPad) * 16 + (j - 32)] = 1; }
     };
-    if (kWinX && tid < s) base[kXOnesRow * kXRow + kXPad + tid] = 1;   // the all-ones row
     if (samp) {                                                        // offset table (caller checked table_usable)
         const int sp = samp_pitch(s), nq = sp >> 2, upa = s * nq;
         const u32 tailmask = (s & 3) ? (1u << (8 * (s & 3))) - 1u : 0xffffffffu;
@@ -1284,9 +1228,7 @@ __device__ __noinline__ void rp_winner_stage(const double *rot4, const uint16_t 
             const uint2 e = ta[u];
             const u32 vm = jq == nq - 1 ? tailmask : 0xffffffffu;
             const u32 raw = gather_quad(patch, e);
-            if (kWinX) {
-                *reinterpret_cast<u32 *>(base + i * kXRow + kXPad + 4 * jq) = (raw ^ 0x80808080u) & vm;
-            } else if (jq < 8) {
+            if (jq < 8) {
                 *reinterpret_cast<u32 *>(base + kTrOff + (i + kWPad) * 32 + 4 * jq) = raw ^ 0x80808080u;
                 *reinterpret_cast<u32 *>(base + kTr1Off + (i + kWPad) * 32 + 4 * jq) = 0x01010101u;
             } else {
@@ -1344,10 +1286,7 @@ __device__ __noinline__ void rp_winner_stage_tab(int a)
         const int u = tid + k * kBlockM;
         if (u < nu) {
             const int i = u / 9, q = u - 9 * i;
-            if (kWinX) {
-                *reinterpret_cast<u32 *>(base + i * kXRow + kXPad + 4 * q) = val[k];
-                if (i == 0) *reinterpret_cast<u32 *>(base + kXOnesRow * kXRow + kXPad + 4 * q) = q < 8 ? 0x01010101u : ones_strip;
-            } else if (q < 8) {
+            if (q < 8) {
                 *reinterpret_cast<u32 *>(base + kTrOff + (i + kWPad) * 32 + 4 * q) = val[k];
                 *reinterpret_cast<u32 *>(base + kTr1Off + (i + kWPad) * 32 + 4 * q) = 0x01010101u;
             } else {
@@ -1502,134 +1441,6 @@ __device__ __forceinline__ void rp_winner_item(int y0, int x0, const double sT, 
         for (int r = 0; r < 4; ++r)
             if (idxv[k][r] >= 0) ccm[idxv[k][r]] = res[k][r];
     if (dbg && tid == 0) dbg[18] = (long long)clock64();
-}
-
-// One pass of the x-shift form: NT tiles (16 x 16 placements each) of one wavefront share the A fragments.
-// tile k of the pass = tile0 + k * tstep (row-major over nty x ntx tiles).
-template <int S, int PITCH, bool ONES, bool BIG, int NT>
-__device__ __forceinline__ void rp_winx_pass(int tile0, int tstep, int ntx, const double sT, const double rT, const bool cT, const u32 *sii)
-{
-    SID_PHASE_LOCALS;
-    float *ccm = tab_ptr<BIG, float>(G, smem, G.ccm_off);
-    const int rh = G.rh, rw = G.rw, wpitch = rp_pitch_bytes(PITCH) ? rp_pitch_bytes(PITCH) : G.wpitch;
-    constexpr bool GS = rp_pitch_is_gs(PITCH);
-    const u32 *siw = GS ? sii + G.gsi : reinterpret_cast<const u32 *>(smem + G.si_off);   // (sum w' kept by the sweep: read when !ONES)
-    int y0[NT], x0[NT];
-    u32 bo[NT][2];                                                     // this lane's window bytes of template row 0: two 8-byte halves
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-        const int t = tile0 + k * tstep, yt = t / ntx, xt = t - yt * ntx;
-        y0[k] = 16 * yt; x0[k] = 16 * xt;
-        bo[k][0] = (u32)(G.win_off + (y0[k] + n_l) * wpitch + x0[k] + 16 * q_l);
-        bo[k][1] = bo[k][0] + 8u;
-        asm("" : "+v"(bo[k][1]));                                      // (two ds_read_b64, not one half-rate ds_read2_b64)
-    }
-    // placements of this lane: row y0 + n, columns x0 + 4 g .. + 3 (accumulator register r = x-shift 4 g + r)
-    int idxv[NT][4]; u32 siv[NT][4]; int swv[NT][4];
-    auto fetch_sii = [&]() {
-#pragma unroll
-        for (int k = 0; k < NT; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int y = y0[k] + n_l, x = x0[k] + 4 * q_l + r;
-                const bool ok = y < rh && x < rw;
-                idxv[k][r] = ok ? y * rw + x : -1;
-                siv[k][r] = sii_at(sii, ok ? y * rw + x : 0);
-                if (!ONES) swv[k][r] = (int)sii_at(siw, ok ? y * rw + x : 0);
-            }
-    };
-    if (GS) fetch_sii();
-    // A fragments: 16 bytes of the padded template row at byte kXPad + 16 g - m
-    const u32 ao = (u32)(G.u_off + kXPad + 16 * q_l - n_l), sha = ao & 3u;
-    Off5 a5 = Off5::make(ao & ~3u);
-    v4i a1 = v4i{0, 0, 0, 0};
-    if (ONES) a1 = align_raw(read_raw5(a5, (u32)(kXOnesRow * kXRow)), sha);
-    v4i acc[NT], acc1[NT];
-#pragma unroll
-    for (int k = 0; k < NT; ++k) { acc[k] = v4i{0, 0, 0, 0}; acc1[k] = v4i{0, 0, 0, 0}; }
-    constexpr int kDepth = 2;
-    constexpr int PB = rp_pitch_bytes(PITCH);
-    Raw5 ra[kDepth]; uint2 rb[kDepth][NT][2];
-    auto rd = [&](int row, int sl) {
-        ra[sl] = read_raw5(a5, (u32)(row * kXRow));
-#pragma unroll
-        for (int k = 0; k < NT; ++k) {
-            const u32 d = (u32)row * (PB ? (u32)PB : (u32)wpitch);
-            rb[sl][k][0] = *reinterpret_cast<const uint2 *>(smem + bo[k][0] + d);
-            rb[sl][k][1] = *reinterpret_cast<const uint2 *>(smem + bo[k][1] + d);
-        }
-    };
-#pragma unroll
-    for (int d = 0; d < kDepth; ++d) rd(d, d);
-#pragma unroll
-    for (int row = 0; row < S; ++row) {
-        const int sl = row % kDepth;
-        const v4i a = align_raw(ra[sl], sha);
-        v4i b[NT];
-#pragma unroll
-        for (int k = 0; k < NT; ++k) b[k] = v4i{(int)rb[sl][k][0].x, (int)rb[sl][k][0].y, (int)rb[sl][k][1].x, (int)rb[sl][k][1].y};
-        if (row + kDepth < S) rd(row + kDepth, sl);
-#pragma unroll
-        for (int k = 0; k < NT; ++k) {
-            acc[k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[k], acc[k], 0, 0, 0);
-            if (ONES) acc1[k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b[k], acc1[k], 0, 0, 0);
-        }
-    }
-    const double nd = G.nd;
-    if (!GS) fetch_sii();
-    float res[NT][4];
-    u32 slowbits = 0;
-    if (cT) {                                                          // a constant template: 1 everywhere (uniform for the angle)
-#pragma unroll
-        for (int k = 0; k < NT; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) res[k][r] = 1.0f;
-    } else {
-        const ncc_norm::Hoisted hc = ncc_norm::Hoisted::make(nd, sT, rT);
-#pragma unroll
-        for (int k = 0; k < NT; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bool sl;
-                res[k][r] = ncc_fast_nobranch(acc[k][r], ONES ? acc1[k][r] : swv[k][r], siv[k][r], hc, sl);
-                slowbits |= (sl && idxv[k][r] >= 0) ? (1u << (4 * k + r)) : 0u;
-            }
-        if (slowbits) {                                                // rare: low-variance windows, rounding boundaries, |q| at or beyond a clamp threshold
-#pragma unroll
-            for (int k = 0; k < NT; ++k)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if ((slowbits >> (4 * k + r)) & 1u) res[k][r] = ncc_flagged(acc[k][r], ONES ? acc1[k][r] : swv[k][r], siv[k][r], hc, rT);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (idxv[k][r] >= 0) ccm[idxv[k][r]] = res[k][r];
-}
-
-template <int S, int PITCH = 0, bool BIG = false>
-__device__ __forceinline__ void rp_winx(int ka, const u32 *gs, long long *dbg_cycles)
-{
-    SID_PHASE_LOCALS;
-    __syncthreads();                                                   // the staged operands are complete
-    if (dbg_cycles && tid == 0) dbg_cycles[13] = (long long)clock64();
-    const double sT = m->sTd[ka], rT = m->rTd[ka];
-    const bool cT = m->constT[ka] != 0;
-    const int nty = (G.rh + 15) >> 4, ntx = (G.rw + 15) >> 4, ntile = nty * ntx;
-    const bool ones = rp_pitch_is_gs(PITCH) ? G.gsi == 0 : G.si_off == 0;
-    // tiles are dealt to the wavefronts round-robin; a wavefront takes its tiles up to three per pass (they share the A fragments)
-    constexpr int kPass = 3;
-    for (int first = wv; first < ntile; first += kPass * kWavesM) {
-        const int left = (ntile - first + kWavesM - 1) / kWavesM;      // tiles of this wavefront from `first` on
-        const int nt = left < kPass ? left : kPass;
-#define SID_WINX(NTv) do { if (ones) rp_winx_pass<S, PITCH, true, BIG, NTv>(first, kWavesM, ntx, sT, rT, cT, gs); \
-                           else rp_winx_pass<S, PITCH, BIG, BIG, NTv>(first, kWavesM, ntx, sT, rT, cT, gs); } while (0)
-        if (nt == 3) SID_WINX(3); else if (nt == 2) SID_WINX(2); else SID_WINX(1);
-#undef SID_WINX
-    }
-    __syncthreads();
 }
 
 template <int S, int PITCH = 0, bool BIG = false>
@@ -1843,7 +1654,7 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
         // (kept accumulators - one group of angles, launch by launch, PMArgs::gs_keep_acc: the table follows sum w'^2, and sum w'
         // is its ones slot)
         G->gsa = 0; G->gsa_rw = 0;
-        if (GS && !BIG && SID_KEEP_ACC_OK(PAIRED) && A.gs_keep_acc && K <= kAnglesPerGroup) {
+        if (GS && !BIG && PAIRED != 0 && A.gs_keep_acc && K <= kAnglesPerGroup) {
             int cp, rpad;
             rp_acc_dims(rh, rw, PAIRED ? 4 * rp_ngroups(PAIRED) : BAND, cp, rpad);
             G->gsa = round_up(npos, 64); G->gsa_rw = cp; G->gsi = 0;
@@ -1952,12 +1763,11 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
     SID_STAMP(5);
 
 #ifndef SID_ABLATE_WINNER
-    if (GS && !BIG && SID_KEEP_ACC_OK(PAIRED) && G->gsa != 0) rp_winner_kept<rp_tab_shift(PAIRED), kSlots / rp_ngroups(PAIRED)>(ka, gs);
+    if (GS && !BIG && PAIRED != 0 && G->gsa != 0) rp_winner_kept<rp_tab_shift(PAIRED), kSlots / rp_ngroups(PAIRED)>(ka, gs);
     else {
         if (K <= kAnglesPerGroup) rp_winner_stage_tab<S, rp_tab_shift(PAIRED)>(ka);
         else rp_winner_stage<S>(A.rot + 4 * ka, samp, A.rows1, A.cols1, ka);
-        if (kWinX) rp_winx<S, PITCH, BIG>(ka, gs, A.dbg_cycles);
-        else rp_winner<S, PITCH, BIG>(ka, gs, A.dbg_cycles);
+        rp_winner<S, PITCH, BIG>(ka, gs, A.dbg_cycles);
     }
 #endif
     SID_STAMP(6);
@@ -1986,3 +1796,20 @@ __global__ __launch_bounds__(BAND == 8 ? 256 : kMaxBlockM, BAND == 8 ? 2 : kOccM
     }
 #undef SID_STAMP
 }
+
+// the instantiation of a row of SID_PM_RP_INSTANCES in this translation unit (rows of its register budget only), nullptr: no such row
+template <int OCC = kOccM>
+PmKernel rp_kernel(int s, int band, int paired, int pitch, bool big)
+{
+#define SID_ROW(S, BAND, PAIRED, PITCH, ROW_OCC, BIG)                                                         \
+    if constexpr (ROW_OCC == OCC) {                                                                           \
+        if (s == S && band == BAND && paired == PAIRED && pitch == PITCH && big == BIG) return pm_kernel_rp<S, BAND, PAIRED, PITCH, BIG>; \
+    }
+    SID_PM_RP_INSTANCES(SID_ROW)
+#undef SID_ROW
+    return nullptr;
+}
+
+}  // namespace
+
+}  // namespace sid

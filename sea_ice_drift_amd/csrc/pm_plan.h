@@ -209,7 +209,7 @@ inline RpLdsLayout big_layout(int wh, int ww, int s, int K, uint32_t flags)
 inline bool keep_acc_policy(const Switches &sw, bool rp, int rpp, int K)
 {
     if (!rp || K > kRpGroup) return false;
-    if (rpp == 0 && !kKeepAccFull) return false;                  // (the full-table kernels carry the code in measurement builds only)
+    if (rpp == 0) return false;                                   // (the full-table kernels do not carry the code: tools/patches/keep_acc_full.patch)
     return sw.keep_acc >= 0 ? sw.keep_acc > 0 : rpp > 0;
 }
 // ... per launch: four slot groups (at most 3 angles, 16 B per placement) everywhere; two groups (at most 7 angles, 32 B) only

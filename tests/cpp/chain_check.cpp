@@ -6,13 +6,6 @@
 #define __device__
 #include "../../sea_ice_drift_amd/csrc/pm_plan.h"
 
-// (pm_plan.h declares what the kernels' translation unit answers; nothing here calls it)
-namespace sid {
-int max_lds_bytes() { return 160 * 1024; }
-bool mfma_img_size_supported(int) { return true; }
-bool mfma_band8_supported(int) { return true; }
-bool rp_pitch_instantiated(int, int, int, int) { return true; }
-}  // namespace sid
 
 using namespace sid;
 using namespace sid::plan;

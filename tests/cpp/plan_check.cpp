@@ -2,6 +2,7 @@
 // tests/test_plan_host.py with g++ alone.  No argument: the matrix of template sides x angle counts x flags x switch sets on a
 // 400 x 400 image 2, one line per violated invariant, then "<n> violations".  `grid FILE s K`: the launch table (count lds band
 // pitch occ) of the points in FILE (n, then c1 r1 c2fg r2fg border per point) on a 10000 x 10000 pair, default switches.
+// `instances`: the table of kernel instantiations (pm_instances.h) against the written-out predicate, over the whole domain.
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
@@ -11,20 +12,16 @@
 #define __device__
 #include "../../sea_ice_drift_amd/csrc/pm_plan.h"
 
-// what the kernels' translation unit answers (pm_kernel_mfma.hip: max_lds_bytes, mfma_*_supported, and the table of
-// instantiations behind rp_kernel_for / rp_occ4_kernel), mirrored for a build without HIP
-namespace sid {
-int max_lds_bytes() { return 160 * 1024; }
-bool mfma_img_size_supported(int s) { return s >= 2 && s <= 64; }
-bool mfma_band8_supported(int s) { return s == 34 || s == 35; }
-bool rp_pitch_instantiated(int band, int paired, int pitch, int occ)
+// What the planner asks about the kernels' instantiations it reads from the table the library ships (pm_instances.h).  The
+// predicate that used to stand in for that table here is its SPECIFICATION now: written out, and compared with the table over
+// the whole domain (`instances`; the pitches the kernels carry and four they do not).
+static bool rp_pitch_spec(int band, int paired, int pitch, int occ)
 {
     if (occ == 4) return band == 4 && (pitch == 104 || pitch == 112) && (paired == 1 || paired == 2);
     const bool common = pitch == 136 || pitch == 168 || pitch == 0;
     if (paired == 0 && band == 8) return common;
     return common || pitch == 104 || pitch == 112 || pitch == 1104;
 }
-}  // namespace sid
 
 using namespace sid;
 using namespace sid::plan;
@@ -193,8 +190,45 @@ static std::vector<Set> switch_sets()
     return v;
 }
 
+// the table against the written-out predicate; prints "<n> instance checks, <m> violations"
+static int check_instances()
+{
+    int checks = 0;
+    for (int band : {4, 8})
+        for (int paired : {0, 1, 2})
+            for (int occ : {3, 4})
+                for (int pitch : {0, 104, 112, 136, 168, 1104, 96, 120, 1112, 2104}) {
+                    CHECK(sid::rp_pitch_instantiated(band, paired, pitch, occ) == rp_pitch_spec(band, paired, pitch, occ),
+                          "band %d paired %d pitch %d occ %d: the table says %d", band, paired, pitch, occ, (int)sid::rp_pitch_instantiated(band, paired, pitch, occ));
+                    ++checks;
+                }
+    // both sides carry the same rows (rp_pitch_instantiated asks side 34), and the default register budget is three per SIMD
+    for (int band : {4, 8})
+        for (int paired : {0, 1, 2})
+            for (int occ : {3, 4})
+                for (int pitch : {0, 104, 112, 136, 168, 1104, 96, 120, 1112, 2104})
+                    for (bool big : {false, true}) {
+                        CHECK(sid::rp_instantiated(34, band, paired, pitch, occ, big) == sid::rp_instantiated(35, band, paired, pitch, occ, big),
+                              "band %d paired %d pitch %d occ %d big %d: sides 34 and 35 differ", band, paired, pitch, occ, (int)big);
+                        ++checks;
+                    }
+    CHECK(sid::rp_pitch_instantiated(4, 1, 104) == sid::rp_pitch_instantiated(4, 1, 104, 3) && sid::rp_pitch_instantiated(8, 0, 104) == sid::rp_pitch_instantiated(8, 0, 104, 3), "default occ");
+    // the other three answers, written out
+    for (int s = -1; s <= 70; ++s) {
+        CHECK(sid::mfma_img_size_supported(s) == (s >= 2 && s <= 64), "mfma_img_size_supported(%d)", s);
+        CHECK(sid::mfma_band8_supported(s) == (s == 34 || s == 35), "mfma_band8_supported(%d)", s);
+        CHECK(sid::mfma_side_arg(s) == ((s == 34 || s == 35) ? s : 0), "mfma_side_arg(%d)", s);
+        checks += 3;
+    }
+    CHECK(sid::max_lds_bytes() == 160 * 1024, "max_lds_bytes");
+    checks += 2;
+    printf("%d instance checks, %d violations\n", checks, bad);
+    return bad > 125 ? 125 : bad;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && !strcmp(argv[1], "instances")) return check_instances();
     if (argc == 5 && !strcmp(argv[1], "grid")) {
         FILE *f = fopen(argv[2], "r");
         if (!f) return 2;

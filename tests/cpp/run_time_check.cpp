@@ -11,19 +11,7 @@
 #define __device__
 #include "../../sea_ice_drift_amd/csrc/pm_plan.h"
 
-// what the kernels' translation unit answers, mirrored for a build without HIP (as in plan_check.cpp)
-namespace sid {
-int max_lds_bytes() { return 160 * 1024; }
-bool mfma_img_size_supported(int s) { return s >= 2 && s <= 64; }
-bool mfma_band8_supported(int s) { return s == 34 || s == 35; }
-bool rp_pitch_instantiated(int band, int paired, int pitch, int occ)
-{
-    if (occ == 4) return band == 4 && (pitch == 104 || pitch == 112) && (paired == 1 || paired == 2);
-    const bool common = pitch == 136 || pitch == 168 || pitch == 0;
-    if (paired == 0 && band == 8) return common;
-    return common || pitch == 104 || pitch == 112 || pitch == 1104;
-}
-}  // namespace sid
+// (what the planner asks about the kernels' instantiations it reads from pm_instances.h, as the library does)
 
 using namespace sid::plan;
 

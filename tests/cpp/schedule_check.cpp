@@ -9,13 +9,6 @@
 #define __device__
 #include "../../sea_ice_drift_amd/csrc/pm_plan.h"
 
-// what the kernels' translation unit answers, mirrored for a build without HIP (as in plan_check.cpp)
-namespace sid {
-int max_lds_bytes() { return 160 * 1024; }
-bool mfma_img_size_supported(int s) { return s >= 2 && s <= 64; }
-bool mfma_band8_supported(int s) { return s == 34 || s == 35; }
-bool rp_pitch_instantiated(int, int, int, int) { return true; }
-}  // namespace sid
 
 using namespace sid;
 using namespace sid::plan;

@@ -123,7 +123,7 @@ def small_matrix_points(s):
 
 
 TINY_SIDES = (2, 3, 4, 5)
-MED_LIST = 256                                                        # kMedList of csrc/pm_kernel_mfma.hip: keys the median ranks by brute force
+MED_LIST = 256                                                        # kMedList of csrc/pm_kernel_base.h: keys the median ranks by brute force
 
 
 def tiny_side_points(s):

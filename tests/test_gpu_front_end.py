@@ -1,4 +1,4 @@
-"""GPU parity of the front end of the row-pair kernels - the window load (ph_window_t, csrc/pm_kernel_mfma.hip) and the box sums of
+"""GPU parity of the front end of the row-pair kernels - the window load (ph_window_t, csrc/pm_kernel_phases.h) and the box sums of
 w'^2 (rp_sums, csrc/pm_kernel_rp.inc) - on a pair made for them: image 1 holds only the bytes 1 and 255, image 2 is image 1 rolled by
 (3, -2) with every 1 turned into 0, so that the re-centred window bytes are the extremes -128 (square 16 384) and 127, plus one
 constant block of 0 and one of 255 (flat windows: sum w'^2 = N * 16 384 and N * 16 129, variance exactly 0).  A packed or byte-wise

@@ -229,7 +229,7 @@ def test_hessian_options_incl_gaussian_smoothing(pm_ctx, c_oracle, flags):
 @pytest.mark.gpu
 @pytest.mark.parametrize('s', [34, 35])
 def test_shortened_normalisation_is_the_specification(pm_ctx, s):
-    """The winner's NCC matrix uses exact_from_sums_fast (pm_kernel_mfma.hip): 2^27 pseudo-random sums, bit for bit
+    """The winner's NCC matrix uses exact_from_sums_fast (pm_kernel_base.h): 2^27 pseudo-random sums, bit for bit
     against the specification's IEEE route; the guard must fire (perfect matches, float32 rounding boundaries)."""
     n, bad, slow = pm_ctx.debug_ncc_selftest(1 << 27, img_size=s, seed=20240917 + s)
     assert n >= 1 << 27

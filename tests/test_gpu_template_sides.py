@@ -1,4 +1,4 @@
-"""GPU parity of the classic one-workgroup-per-point kernel (`pm_kernel_mfma<0, 4, paired>`, csrc/pm_kernel_mfma.hip) at its
+"""GPU parity of the classic one-workgroup-per-point kernel (`pm_kernel_mfma<0, 4, paired>`, csrc/pm_kernel_classic.h) at its
 run-time template sides - every side 2 .. 64 but 34 and 35, which the row-pair kernels take - and of the Hessian code of every
 kernel family on NCC matrices of 2 .. 14 placements per axis.
 

@@ -26,6 +26,19 @@ def test_plan_invariants(tmp_path):
     assert p.returncode == 0 and p.stdout.strip().endswith(' 0 violations'), p.stdout[-3000:]
 
 
+def test_instance_table_against_the_written_predicate(tmp_path):
+    """What the planner is told about the kernels' instantiations comes from the table the library ships (csrc/pm_instances.h).
+    The predicate that plan_check.cpp used to answer with is asserted against that table over the whole domain: band 4 / 8 x
+    paired 0 / 1 / 2 x occ 3 / 4 x the six pitches the kernels carry and four they do not (120 checks); both template sides carry
+    the same rows (240); the default register budget (1); mfma_img_size_supported, mfma_band8_supported and the classic kernel's
+    side argument for sides -1 .. 70 (216); max_lds_bytes (1)."""
+    p = subprocess.run([_build(tmp_path), 'instances'], stdout=subprocess.PIPE, universal_newlines=True)
+    print(p.stdout[-3000:])
+    m = re.search(r'(\d+) instance checks, (\d+) violations\s*$', p.stdout)
+    assert p.returncode == 0 and m, p.stdout[-3000:]
+    assert int(m.group(1)) == 120 + 240 + 2 + 216 and int(m.group(2)) == 0
+
+
 def test_plan_of_the_benchmark_grid(tmp_path):
     """The launches of the benchmark grid (count, LDS bytes, band, window pitch, wavefronts per SIMD) are those the library
     printed under SID_PM_VERBOSE=1 on an MI355X before the planner was split off (tests/golden/plan_bench_launches.txt)."""
