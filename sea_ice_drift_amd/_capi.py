@@ -67,6 +67,10 @@ CORR_TILE = (8, 64)                                       # SID_CORR_TILE_ROWS, 
 TRACK_SYMBOLS = ('sid_track_points', 'sid_track_points_device', 'sid_track_last_error', 'sid_track_release')
 TRACK_CLOSED = 1                                          # SID_TRACK_CLOSED
 TRACK_BRUTE_CELLS = 64                                    # SID_TRACK_BRUTE_CELLS: grids below it look at every cell for every point
+# include/sid_ftg.h: guided feature matching, Hamming k=2 within a search radius
+FTG_SYMBOLS = ('sid_ftg_knn2', 'sid_ftg_knn2_device', 'sid_ftg_workspace_bytes', 'sid_ftg_debug_plan', 'sid_ftg_last_error',
+               'sid_ftg_release')
+FTG_MAX_TRAIN = 1 << 22                                   # the index bits of the ordering key: n2 below it
 
 # every symbol include/sid_prep.h declares (sigma0 preparation: dB, HH correction, mask, detrend; same library)
 PREP_SYMBOLS = ('sid_prep_subsample', 'sid_prep_apply', 'sid_prep_spatial_mean', 'sid_prep_debug_log10', 'sid_prep_last_error')
@@ -233,6 +237,16 @@ def lib():
         L.sid_track_points_device.argtypes = [vp] * 5 + [i64, i64, C.c_int, C.c_uint32, vp, vp, i64, vp, vp, vp, vp]
         L.sid_track_last_error.restype = C.c_char_p
         L.sid_track_release.argtypes = [C.c_int]
+    if hasattr(L, 'sid_ftg_knn2'):               # (absent from the libraries of earlier rounds that A/B runs load through SID_PM_LIB)
+        vp, i64 = C.c_void_p, C.c_int64
+        sets = [vp, vp, vp, i64, vp, vp, vp, i64, C.c_double]
+        L.sid_ftg_knn2.argtypes = [C.c_int] + sets + [vp] * 3
+        L.sid_ftg_knn2_device.argtypes = sets + [vp] * 5
+        L.sid_ftg_workspace_bytes.argtypes = [i64, i64]
+        L.sid_ftg_workspace_bytes.restype = i64
+        L.sid_ftg_debug_plan.argtypes = [i64, i64] + [C.c_double] * 5 + [vp]
+        L.sid_ftg_last_error.restype = C.c_char_p
+        L.sid_ftg_release.argtypes = [C.c_int]
     if hasattr(L, 'sid_prep_apply'):
         vp, plane = C.c_void_p, [C.c_void_p, C.c_int64]
         L.sid_prep_subsample.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64] + plane + plane + [C.c_int, C.c_float, C.c_int64, vp, vp]
@@ -298,7 +312,7 @@ def _p(a, t):
 
 def release_workspaces(device=-1):
     """Hand the cached device memory of the detector, the matcher, the first-guess evaluation and the deformation back
-    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``, ``sid_corr_release``, ``sid_track_release``; -1: every device).  No call on that device may be in flight.
+    (``sid_orb_release``, ``sid_ft_release``, ``sid_fg_release``, ``sid_defor_release``, ``sid_grid_release``, ``sid_warp_release``, ``sid_corr_release``, ``sid_track_release``, ``sid_ftg_release``; -1: every device).  No call on that device may be in flight.
     A process that never loaded the library has nothing cached: this returns without loading it (it is registered with
     atexit through pmlib.release_contexts, and loading means importing torch and initialising the GPU - not at interpreter
     shutdown, and not in a process that only used the host code)."""
@@ -306,7 +320,7 @@ def release_workspaces(device=-1):
         return
     L = _lib
     for name in ('sid_orb_release', 'sid_ft_release', 'sid_fg_release', 'sid_defor_release', 'sid_grid_release', 'sid_warp_release',
-                 'sid_corr_release', 'sid_track_release'):
+                 'sid_corr_release', 'sid_track_release', 'sid_ftg_release'):
         if hasattr(L, name):
             getattr(L, name)(int(device))
 
@@ -685,7 +699,7 @@ def _checker(unit, index_error=None):
 _ft_check, _stage_check, _fg_check = _checker('sid_ft'), _checker('sid_stage'), _checker('sid_fg')
 _defor_check, _grid_check, _warp_check = _checker('sid_defor', DEFOR_ERR_INDEX), _checker('sid_grid'), _checker('sid_warp')
 _prep_check, _mask_check, _resize_check = _checker('sid_prep'), _checker('sid_mask'), _checker('sid_resize')
-_corr_check, _track_check = _checker('sid_corr'), _checker('sid_track')
+_corr_check, _track_check, _ftg_check = _checker('sid_corr'), _checker('sid_track'), _checker('sid_ftg')
 
 
 def _vp(p):
@@ -733,6 +747,75 @@ def ft_knn2_device(d_desc1, n1, d_desc2, n2, d_idx, d_dist, d_workspace, stream=
     ft_workspace_bytes(n1, n2) bytes (16-byte aligned)."""
     _ft_check(lib().sid_ft_knn2_device(_vp(d_desc1), int(n1), _vp(d_desc2), int(n2), _vp(d_idx), _vp(d_dist), _vp(d_workspace),
                                        _vp(stream)))
+
+
+def _ftg_radius(radius):
+    """The radius of the guided matcher as a float: finite and >= 0, or ValueError (before any device call)."""
+    r = float(radius)
+    if not (np.isfinite(r) and r >= 0.0):
+        raise ValueError('search radius must be finite and >= 0, got %r' % (radius,))
+    return r
+
+
+def _ftg_set(desc, xy, what):
+    """One side of the guided matcher: descriptors uint8 [n, 32] and positions [n, 2] -> (desc, x, y) C-contiguous."""
+    d = np.asarray(desc)
+    if d.dtype != np.uint8 or d.ndim != 2 or d.shape[1] != 32:
+        raise TypeError('%s descriptors must be a uint8 array of shape (n, 32)' % what)
+    p = np.asarray(xy, dtype=np.float64)
+    if p.ndim != 2 or p.shape != (len(d), 2):
+        raise ValueError('%s positions must have shape (%d, 2): one (x, y) per descriptor, got %r' % (what, len(d), p.shape))
+    return np.ascontiguousarray(d), np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+
+
+def ftg_knn2(desc1, q_xy, desc2, t_xy, radius, device=0, want_count=True):
+    """Two Hamming-nearest train descriptors of every query among those within ``radius`` pixels of the query's position:
+    include/sid_ftg.h sid_ftg_knn2.
+
+    desc1 [n1,32], desc2 [n2,32] uint8; q_xy [n1,2]: the PREDICTED positions of the queries in the train image's pixel frame,
+    t_xy [n2,2]: the train positions -> (idx [n1,2] int32, dist [n1,2] int32, count [n1] int32 or None), -1 where absent.
+    Shapes, dtypes and the radius are checked before any device call (TypeError / ValueError)."""
+    d1, qx, qy = _ftg_set(desc1, q_xy, 'query')
+    d2, tx, ty = _ftg_set(desc2, t_xy, 'train')
+    r = _ftg_radius(radius)
+    if len(d2) >= FTG_MAX_TRAIN:
+        raise ValueError('at most %d train descriptors' % (FTG_MAX_TRAIN - 1))
+    n1 = len(d1)
+    idx = np.empty((n1, 2), dtype=np.int32)
+    dist = np.empty((n1, 2), dtype=np.int32)
+    count = np.empty(n1, dtype=np.int32) if want_count else None
+    if n1:                                                               # (an empty array has no address to hand over)
+        _ftg_check(lib().sid_ftg_knn2(int(device), _vp(d1), _vp(qx), _vp(qy), n1, _vp(d2), _vp(tx), _vp(ty), len(d2), r,
+                                      _vp(idx), _vp(dist), _vp(count)))
+    return idx, dist, count
+
+
+def ftg_workspace_bytes(n1, n2):
+    """Bytes of workspace ftg_knn2_device needs (include/sid_ftg.h sid_ftg_workspace_bytes)."""
+    return int(lib().sid_ftg_workspace_bytes(int(n1), int(n2)))
+
+
+def ftg_knn2_device(d_desc1, d_qx, d_qy, n1, d_desc2, d_tx, d_ty, n2, radius, d_idx, d_dist, d_count, d_workspace, stream=0):
+    """ftg_knn2 on device-resident buffers, asynchronous on ``stream`` (include/sid_ftg.h sid_ftg_knn2_device): raw device
+    addresses (torch ``data_ptr()``; d_count 0 for none) of descriptors [n,32] uint8 (16-byte aligned), positions [n] float64,
+    idx and dist [n1,2] int32, count [n1] int32 and a workspace of ftg_workspace_bytes(n1, n2) bytes (16-byte aligned)."""
+    r = _ftg_radius(radius)
+    _ftg_check(lib().sid_ftg_knn2_device(_vp(d_desc1), _vp(d_qx), _vp(d_qy), int(n1), _vp(d_desc2), _vp(d_tx), _vp(d_ty), int(n2), r,
+                                         _vp(d_idx), _vp(d_dist), _vp(d_count), _vp(d_workspace), _vp(stream)))
+
+
+class _FtgPlan(C.Structure):
+    """struct sid_ftg_plan (include/sid_ftg.h)."""
+    _fields_ = [(name, C.c_double) for name in ('x0', 'y0', 'cell_x', 'cell_y')] + \
+               [(name, C.c_int64) for name in ('nx', 'ny', 'axis_cap', 'max_items', 'workspace_bytes')]
+
+
+def ftg_debug_plan(n1, n2, box, radius):
+    """What csrc/ft_guided_plan.h computes for n1 queries, n2 train points with the bounding box ``box`` = (x_lo, x_hi, y_lo,
+    y_hi) and ``radius`` (include/sid_ftg.h sid_ftg_debug_plan; test support, no device call): a dict of the struct's fields."""
+    s = _FtgPlan()
+    _ftg_check(lib().sid_ftg_debug_plan(int(n1), int(n2), *[float(v) for v in box], float(radius), C.byref(s)))
+    return {name: getattr(s, name) for name, _ in _FtgPlan._fields_}
 
 
 class _FgRoute(C.Structure):

@@ -1,5 +1,5 @@
 // host_util.h - the host scaffold of the units beside the pattern-matching core (ft_match, stage, orb, first_guess, defor, prep,
-// landmask, drift_grid, warp, resize, local_corr, track).  Host code only.  Everything lives in an anonymous namespace: every unit
+// landmask, drift_grid, warp, resize, local_corr, track, ft_guided).  Host code only.  Everything lives in an anonymous namespace: every unit
 // keeps its OWN thread-local error text (sid_grid_last_error never shows sid_warp's message) and its own pools.
 // pm_capi.hip / pm_large.hip keep their own error handling, which is tied to the handle.
 #pragma once

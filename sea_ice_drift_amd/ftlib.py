@@ -108,20 +108,95 @@ def _get_matches(descriptors1, descriptors2, device=0, verbose=False):
     return _capi.ft_knn2(descriptors1, descriptors2, device=device)
 
 
-def match(kp1, descr1, kp2, descr2, ratio_test=0.7, device=0, verbose=False):
-    """Ratio-tested correspondences between two key-point sets -> Matches (query order)."""
-    idx, dist = _get_matches(descr1, descr2, device=device, verbose=verbose)
-    keep = mask_lowe_ratio(dist, ratio_test)
-    _say(verbose, 'Ratio test %f found %d keypoints', ratio_test, int(keep.sum()))
-    a, b = _xy(kp1)[keep], _xy(kp2)[idx[keep, 0]]
+def mask_guided_ratio(dist, count, ratio, accept_lone=False):
+    """Lowe's test for the guided matcher: the runner-up is the second nearest WITHIN the search radius.  A query with fewer
+    than two candidates has none: it is dropped unless ``accept_lone`` and it has one; a query with no candidate always is."""
+    count = np.asarray(count)
+    keep = (count >= 2) & mask_lowe_ratio(dist, ratio)
+    if accept_lone:
+        keep |= count == 1
+    return keep
+
+
+def _guided_pairs(descr1, pos1, descr2, pos2, radius, ratio_test, accept_lone, device):
+    """(query index, train index) of the pairs the guided matcher and its ratio test keep, in query order."""
+    idx, dist, count = _capi.ftg_knn2(descr1, pos1, descr2, pos2, radius, device=device)
+    q = np.flatnonzero(mask_guided_ratio(dist, count, ratio_test, accept_lone))
+    return q, idx[q, 0]
+
+
+def match(kp1, descr1, kp2, descr2, ratio_test=0.7, device=0, verbose=False, search_radius=None, predicted=None,
+          cross_check=False, accept_lone=False):
+    """Ratio-tested correspondences between two key-point sets -> Matches (query order).
+
+    ``search_radius=None`` is the reference's matcher: every descriptor of set 1 against every descriptor of set 2.
+    ``search_radius=r`` (pixels of image 2; not a reference keyword) is guided matching (include/sid_ftg.h): the two nearest
+    neighbours of a key point are searched among the key points of set 2 within ``r`` of ``predicted`` - an ``(n1, 2)`` array,
+    the positions of ``kp1`` in image 2's pixel frame, required then.  A key point with fewer than two candidates has no
+    runner-up for the ratio test: it is dropped unless ``accept_lone`` and it has one.  ``cross_check``: the same search with
+    the roles swapped - ``kp2`` at their own positions against ``kp1`` at the predicted ones - and a pair (i, j) is kept only
+    if i is also j's nearest."""
+    if search_radius is None:
+        if predicted is not None or cross_check or accept_lone:
+            raise ValueError('predicted, cross_check and accept_lone belong to guided matching: give search_radius')
+        idx, dist = _get_matches(descr1, descr2, device=device, verbose=verbose)
+        keep = mask_lowe_ratio(dist, ratio_test)
+        _say(verbose, 'Ratio test %f found %d keypoints', ratio_test, int(keep.sum()))
+        a, b = _xy(kp1)[keep], _xy(kp2)[idx[keep, 0]]
+        return Matches(a[:, 0], a[:, 1], b[:, 0], b[:, 1])
+    if predicted is None:
+        raise ValueError('search_radius needs predicted: the positions of kp1 in the pixel frame of image 2')
+    xy1, xy2 = _xy(kp1), _xy(kp2)
+    pred = np.asarray(predicted, dtype=np.float64)
+    if pred.shape != xy1.shape:
+        raise ValueError('predicted must have shape %r, one (x, y) per key point of image 1; got %r' % (xy1.shape, pred.shape))
+    d1, d2 = np.asarray(descr1).reshape(-1, 32), np.asarray(descr2).reshape(-1, 32)
+    q, t = _guided_pairs(d1, pred, d2, xy2, search_radius, ratio_test, accept_lone, device)
+    _say(verbose, 'Guided ratio test %f within %s px found %d keypoints', ratio_test, search_radius, len(q))
+    if cross_check:
+        back_q, back_t = _guided_pairs(d2, xy2, d1, pred, search_radius, ratio_test, accept_lone, device)
+        nearest_of = np.full(len(xy2), -1, dtype=np.int64)
+        nearest_of[back_q] = back_t
+        mutual = nearest_of[t] == q
+        _say(verbose, 'Cross check: %d -> %d', len(q), int(mutual.sum()))
+        q, t = q[mutual], t[mutual]
+    a, b = xy1[q], xy2[t]
     return Matches(a[:, 0], a[:, 1], b[:, 0], b[:, 1])
+
+
+def drift_limit_pixels(n1, n2, max_speed=0.5, max_drift=None):
+    """The limit of ``mask_drift_limit`` - ``max_speed`` m/s over the time between the images when both carry a time stamp,
+    else ``max_drift`` metres; neither available is a ValueError - in pixels of image 2, rounded up: divided by the smallest
+    metres per pixel along columns and rows at the centre and the four corners of image 2, plus 5 %.  A search radius for
+    ``match`` that loses nothing ``mask_drift_limit`` would keep."""
+    if _has_time(n1) and _has_time(n2):
+        metres = max_speed * abs((n2.time_coverage_start - n1.time_coverage_start).total_seconds())
+    elif max_drift is None:
+        raise ValueError('the images carry no time stamp and max_drift is not set: give max_drift, the largest '
+                         'plausible displacement between the two images in metres')
+    else:
+        metres = float(max_drift)
+    rows, cols = n2.shape()[0], n2.shape()[1]
+    x = np.array([cols / 2., 0., float(cols), 0., float(cols)])             # (corner-based pixel coordinates, as get_corners)
+    y = np.array([rows / 2., 0., 0., float(rows), float(rows)])
+    sx, sy = np.where(x + 1 <= cols, 1., -1.), np.where(y + 1 <= rows, 1., -1.)             # (the unit step stays on the raster)
+    per_pixel = 1000. * np.concatenate([great_circle_km(n2, x, y, n2, x + sx, y), great_circle_km(n2, x, y, n2, x, y + sy)])
+    smallest = float(per_pixel.min())
+    if not smallest > 0:
+        raise ValueError('the georeference of image 2 maps neighbouring pixels to one place')
+    return int(np.ceil(1.05 * metres / smallest))
 
 
 # --------------------------------------------------------------------------- the pipeline
 def track(n1, n2, detector, domainMargin=0, ratio_test=0.7, max_speed=0.5, max_drift=None, psi=200, order=2,
-          device=0, verbose=False, concurrent_detection=False, detect_devices=None, **detector_kwargs):
+          device=0, verbose=False, concurrent_detection=False, detect_devices=None, search_radius=None, cross_check=False,
+          accept_lone=False, **detector_kwargs):
     """Detector -> domain masks -> matcher + ratio mask -> drift mask -> model mask (ftlib.py:259-281).
     Fewer than two key points on either side at any stage ends with four empty arrays.
+    ``search_radius`` (pixels of image 2, or ``'max_drift'`` = ``drift_limit_pixels``; None: the reference's matcher):
+    guided matching around the no-drift position of every key point of image 1, the chain of georeferences
+    ``n2.transform_points(*n1.transform_points(x1, y1, 0), 1)``; ``cross_check``, ``accept_lone``: see ``match``.  The drift
+    and model masks run afterwards all the same, so a generous radius costs time, never correctness.
     ``concurrent_detection``: the two images on two host threads (the package's own detector only: its per-level host
     work - candidate selection, sorting - then runs beside the other image's kernels; the results do not depend on it).
     ``detect_devices``: (GPU of image 1, GPU of image 2), handed to the detector as ``device=`` - with
@@ -147,7 +222,19 @@ def track(n1, n2, detector, domainMargin=0, ratio_test=0.7, max_speed=0.5, max_d
         if keep.sum() < 2:
             return _EMPTY
         sets[this] = (_take(kp, keep), descr[keep])
-    m = match(sets[0][0], sets[0][1], sets[1][0], sets[1][1], ratio_test=ratio_test, device=device, verbose=verbose)
+    guided = {}
+    if search_radius is not None:
+        if isinstance(search_radius, str):
+            if search_radius != 'max_drift':
+                raise ValueError("search_radius is a number of pixels or 'max_drift', got %r" % (search_radius,))
+            search_radius = drift_limit_pixels(n1, n2, max_speed=max_speed, max_drift=max_drift)
+        xy1 = _xy(sets[0][0])
+        col, row = n2.transform_points(*n1.transform_points(xy1[:, 0], xy1[:, 1], 0), 1)
+        guided = dict(search_radius=search_radius, predicted=np.stack([col, row], axis=1), cross_check=cross_check,
+                      accept_lone=accept_lone)
+    elif cross_check or accept_lone:
+        raise ValueError('cross_check and accept_lone belong to guided matching: give search_radius')
+    m = match(sets[0][0], sets[0][1], sets[1][0], sets[1][1], ratio_test=ratio_test, device=device, verbose=verbose, **guided)
     keep = mask_drift_limit(n1, n2, m, max_speed=max_speed, max_drift=max_drift)
     _say(verbose, 'MaxDrift filter: %d -> %d', len(keep), int(keep.sum()))
     m = _subset(m, keep)
@@ -174,13 +261,16 @@ def find_key_points(image, edgeThreshold=34, nFeatures=100000, nLevels=7, patchS
 
 
 def get_match_coords(keyPoints1, descriptors1, keyPoints2, descriptors2, matcher=None, norm=None,
-                     ratio_test=0.7, verbose=False, device=0, **kwargs):
+                     ratio_test=0.7, verbose=False, device=0, search_radius=None, predicted=None, cross_check=False,
+                     accept_lone=False, **kwargs):
     """Signature of ftlib.py:64-90 -> x1, y1, x2, y2.  Only the reference's default matcher (brute force,
-    Hamming) exists on the device: passing ``matcher`` / ``norm`` raises ``NotImplementedError``."""
+    Hamming) exists on the device: passing ``matcher`` / ``norm`` raises ``NotImplementedError``.
+    ``search_radius``, ``predicted``, ``cross_check``, ``accept_lone`` (not reference keywords): guided matching, see ``match``."""
     if matcher is not None or norm is not None:
         raise NotImplementedError('only the brute-force Hamming matcher (the reference default) is implemented')
     return tuple(match(keyPoints1, descriptors1, keyPoints2, descriptors2, ratio_test=ratio_test, device=device,
-                       verbose=verbose))
+                       verbose=verbose, search_radius=search_radius, predicted=predicted, cross_check=cross_check,
+                       accept_lone=accept_lone))
 
 
 def domain_filter(n, keyPoints, descr, domain, domainMargin=0, verbose=False, **kwargs):
@@ -214,8 +304,11 @@ def feature_tracking(n1, n2, find_key_points=find_key_points, **kwargs):
     ``devices`` (not a reference keyword; the forms of ``pmlib.resolve_devices``): the package's detector finds the key
     points of image 1 on the first GPU named and those of image 2 on the second (the same, if only one is named), on two
     threads; the matcher runs on the first.  The result does not depend on it.  A detector passed as
-    ``find_key_points=`` is called as without it."""
-    own = ('domainMargin', 'ratio_test', 'max_speed', 'max_drift', 'psi', 'order', 'device', 'verbose')
+    ``find_key_points=`` is called as without it.
+    ``search_radius`` (pixels of image 2 or ``'max_drift'``), ``cross_check``, ``accept_lone`` (not reference keywords): guided
+    matching around the no-drift position of every key point, see ``track`` and ``match``; they do not reach the detector."""
+    own = ('domainMargin', 'ratio_test', 'max_speed', 'max_drift', 'psi', 'order', 'device', 'verbose', 'search_radius',
+           'cross_check', 'accept_lone')
     is_own = find_key_points is globals()['find_key_points']
     detect_devices = None
     if kwargs.get('devices') is not None:
